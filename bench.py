@@ -8,10 +8,13 @@ A *step* is one pass of the hot path — tokenise + NFA walk (+ heavy path) +
 CSR finalisation, i.e. emqx_router:match_routes/1's filter sets for a whole
 batch — over one batch of synthetic topics already resident in HBM.
 The steps run one batch at a time on one HIP stream, so the walk's HIP-event
-time is its own (the roofline's kernel time); the same steps with two batches
-in flight (two streams with their own workspaces: one batch's sort, scan and
-compaction beside the next one's walk) are timed after them and reported as
-the line's `pipelined` (`--streams 2` makes that the timed mode instead).
+time is its own (the roofline's kernel time).  A plain run does no more than
+that: set-up, warm-up, the timed steps, the line.  With `--full` the same steps
+with two batches in flight (two streams with their own workspaces: one batch's
+sort, scan and compaction beside the next one's walk) are timed after them and
+reported as the line's `pipelined` (`--streams 2` makes that the timed mode
+instead), and so are the other row form, the host-visible path, the CPU
+baseline and, at N>1, the sharded leg.
 
 Layouts (emqx_amd/dist.py), named in the line's config.workload:
   replicate (default)  every GPU holds the 10M-filter table and matches its own
@@ -26,10 +29,11 @@ Layouts (emqx_amd/dist.py), named in the line's config.workload:
                        broadcast, counts and ids gathered to rank 0 over RCCL
                        and merged by the HIP merge kernel -> "strong".
 
-At N>1 the replicate `value` is followed by the prefix layout timed on the
-same node (the line's `sharded`; --sharded-layout shard for the round-3 one).
+At N>1 with --full the replicate `value` is followed by the prefix layout timed
+on the same node (the line's `sharded`; --sharded-layout shard for the round-3 one).
 
     python bench.py [--gpus N --steps K --warmup W] [--config c2] [--mode replicate|prefix|shard]
+                    [--full] [--dump-outputs DIR]
 
 Rank 0 prints ONE JSON line on stdout; progress goes to stderr.
 """
@@ -245,6 +249,72 @@ def host_batcher_curve(gm, t, mode, sizes=(1024, 4096, 16384, 65536), depth: int
             "sweep": out,
             "what": "saturated batcher: full batches, `depth` tickets in flight; latency = submit -> wait-return "
                     "of one batch (a caller also waits up to linger_ms for its batch to fill)"}
+
+
+DUMP_SEED = 20240611
+DUMP_MAX_TOPICS = 1 << 20
+DUMP_MAX_IDS = 3 << 20       # 24 MB of float64 filter ids
+DUMP_MAX_SUBS = 2 << 20      # 16 MB of float64 subscriber ids
+
+
+def dump_outputs(out_dir, row, ids, tops, n, fan=None):
+    """Write one step's result as DIR/<name>.npy (--dump-outputs), under 64 MB
+    in all.  `row` / `ids` are the step's CSR on the device, `tops` its row ->
+    topic map (None: rows in input order), `fan` the fan-out's (delivery row
+    starts, subscriber ids) or None.  A row is an order-free set and the row
+    order follows the walk's sort key, so the files hold a form that does not
+    depend on either: a seeded sample of input topics (the first K of a fixed
+    permutation, K <= 2^20 and as many as fit the id budgets), each one's
+    count and its ids ascending; plus the whole step's totals."""
+    import torch
+    dev = row.device
+    u32 = 0xFFFFFFFF
+    row = row[:n + 1]
+    # input topic -> its row
+    if tops is not None:
+        rowof = torch.empty(n, dtype=torch.int64, device=dev)
+        rowof.scatter_(0, tops[:n].to(torch.int64) & u32, torch.arange(n, dtype=torch.int64, device=dev))
+    else:
+        rowof = torch.arange(n, dtype=torch.int64, device=dev)
+    perm = torch.from_numpy(np.random.default_rng(DUMP_SEED).permutation(n)[:DUMP_MAX_TOPICS]).to(dev)
+    csrs = [(row, ids, DUMP_MAX_IDS)] + ([(fan[0][:n + 1], fan[1], DUMP_MAX_SUBS)] if fan else [])
+    k = len(perm)
+    for r, _, room in csrs:   # as many topics of the permutation as fit every budget
+        cnt = (r[1:] - r[:-1])[rowof[perm]]
+        k = min(k, int(torch.count_nonzero(torch.cumsum(cnt, 0) <= room).item()))
+    sample = torch.sort(perm[:k]).values
+    rows = rowof[sample]
+
+    def gather(r, vals):
+        """(count per sampled topic, its values ascending, concatenated)"""
+        start, cnt = r[rows], r[rows + 1] - r[rows]
+        tot = int(cnt.sum().item())
+        slot = torch.repeat_interleave(torch.arange(k, dtype=torch.int64, device=dev), cnt, output_size=tot)
+        first = torch.cumsum(cnt, 0) - cnt
+        v = vals[start[slot] + (torch.arange(tot, dtype=torch.int64, device=dev) - first[slot])].to(torch.int64) & u32
+        v = torch.sort((slot << 32) | v).values & u32
+        return cnt, v
+
+    def total(r, vals):
+        m = int(r[n].item())
+        return [m, int((vals[:m].to(torch.int64) & u32).sum().item())]
+
+    cnt, v = gather(row, ids)
+    out = {"topic_index": sample.cpu().numpy().astype(np.float64),
+           "match_counts": cnt.cpu().numpy().astype(np.float32),
+           "match_ids": v.cpu().numpy().astype(np.float64)}
+    totals = [n] + total(row, ids)
+    if fan:
+        cnt, v = gather(fan[0][:n + 1], fan[1])
+        out["delivery_counts"] = cnt.cpu().numpy().astype(np.float32)
+        out["delivery_subs"] = v.cpu().numpy().astype(np.float64)
+        totals += total(fan[0], fan[1])
+    out["totals"] = np.array(totals, dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"[rank 0] outputs of the last timed step ({k} sampled topics, "
+        f"{sum(a.nbytes for a in out.values()) / 1e6:.1f} MB) in {out_dir}")
 
 
 def _heartbeat(period: float = 30.0):
@@ -589,7 +659,27 @@ def main():
                          "(BASELINE C2 as worded: broadcast + RCCL gather + GPU merge; with fan-out, fan-out on "
                          "the owner shard + a reduce of per-topic delivery totals), reported as the line's "
                          "`sharded`")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU baseline, the host-visible path "
+                         "and the batcher's operating points, the other stream setting (`pipelined` / `serial`), "
+                         "the other row form (`rows_other`), the isolated walk at --streams > 1, the sharded leg "
+                         "at N > 1 (or --sharded-leg on) and the prefix layout's census step (its roofline and "
+                         "stats).  Without it a run sets up, warms up, times the steps and prints the line with "
+                         "those entries null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed to DIR/<name>.npy "
+                         "(rank 0, replicate layout): for a fixed, seeded sample of the batch's topics their input "
+                         "indices (topic_index), match counts (match_counts) and matched filter ids, ascending "
+                         "within each topic (match_ids); with fan-out also delivery_counts and delivery_subs; "
+                         "and the whole step's totals (totals: topics, ids, sum of ids[, deliveries, sum of "
+                         "subscriber ids]).  Rows are order-free sets, so the form is the same for every walk "
+                         "order and row form")
     args = ap.parse_args()
+    full = args.full
+    if args.sharded_leg == "on" and not full:
+        ap.error("--sharded-leg on needs --full")
+    if args.dump_outputs and args.mode != "replicate":
+        ap.error("--dump-outputs: replicate layout only")
     fanout = args.fanout == "on" or (args.fanout == "auto" and args.config in ("c3", "c4"))
     _heartbeat()
 
@@ -637,8 +727,8 @@ def main():
     gm = GpuMatcher(local, max_batch=nt)
     t0 = time.time()
     nstreams = 1 if (shard or prefix or fanout) else max(1, args.streams)
-    piped = args.pipelined == "on" and args.mode == "replicate" and not fanout and nstreams == 1
-    serial_leg = args.pipelined == "on" and args.mode == "replicate" and not fanout and nstreams > 1
+    piped = full and args.pipelined == "on" and args.mode == "replicate" and not fanout and nstreams == 1
+    serial_leg = full and args.pipelined == "on" and args.mode == "replicate" and not fanout and nstreams > 1
     nbuf = 2 if piped else nstreams
     streams = [torch.cuda.Stream(dev) for _ in range(nbuf)]
     stream = streams[0]
@@ -781,8 +871,13 @@ def main():
         assert deliveries <= fcap, (deliveries, fcap)
     wc = gm.walk_counters()
     gm.set_timing(False)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's buffers, before any other leg runs over them
+        i = (bufs["k"] - 1) % bufs["ns"]
+        dump_outputs(args.dump_outputs, bufs["rows"][i], bufs["idss"][i],
+                     bufs["tops"][i] if bufs["walk_rows"] else None, n, (d_drow, d_sub) if fanout else None)
     iso_ms = None
-    if nstreams > 1:
+    if full and nstreams > 1:
         # the walk alone (one stream, nothing overlapping it), untimed: the
         # kernel's own speed next to its time inside the overlapped steps
         gm.set_timing(True)
@@ -843,7 +938,7 @@ def main():
                              "workspaces and output buffers)"}
         bufs["ns"], bufs["k"] = nstreams, 0
     rows_other = None
-    if leg is None and not fanout:
+    if full and leg is None and not fanout:
         # the same steps with the other row form (input order <-> walk order), reported beside `value`
         bufs["walk_rows"], bufs["k"] = not bufs["walk_rows"], 0
         for _ in range(2):
@@ -867,7 +962,7 @@ def main():
     merged_ids = leg.merged_ids() if leg is not None else None
     if args.x_orders and leg is None:
         order_experiment(args, gm, run_local, bufs, dev, n)
-    run_sharded = leg is None and (args.sharded_leg == "on" or (args.sharded_leg == "auto" and world > 1))
+    run_sharded = full and leg is None and (args.sharded_leg == "on" or (args.sharded_leg == "auto" and world > 1))
 
     units_per_step = n if shard else n * world
     value = units_per_step * args.steps / elapsed
@@ -875,32 +970,38 @@ def main():
 
     # ---- roofline (dominant kernel = k_walk), SURVEY §8d byte model ----
     walk_ms = tim["walk_ms"] / max(1, tim["walk_launches"])
-    if prefix:
-        # one walk launch per received slot: the byte model over the step's
-        # totals (an untimed census step), the kernel time over its launches
-        cz = leg.census()
-        sum_d, n_ids, visited, n_walked = cz["levels"], cz["ids"], cz["visited"], cz["topics"]
+    if prefix and not full:
+        # the prefix layout's byte model needs a census step of its own (--full)
+        sum_d = n_ids = visited = n_walked = walk_bytes = achieved = path_bytes = None
         walk_ms *= world
     else:
-        sum_d = levels_sum(t.blob, t.off)
-        n_ids, visited, n_walked = st["n_ids"], st["visited"], n
-    walk_bytes = 8 * sum_d + 32 * visited + 4 * (n_ids + n_walked)
-    achieved = walk_bytes / (walk_ms * 1e-3) / 1e9
-    path_bytes = (nbytes + 4 * n) + 16 * sum_d + 32 * visited + 4 * (n_ids + n)
+        if prefix:
+            # one walk launch per received slot: the byte model over the step's
+            # totals (an untimed census step), the kernel time over its launches
+            cz = leg.census()
+            sum_d, n_ids, visited, n_walked = cz["levels"], cz["ids"], cz["visited"], cz["topics"]
+            walk_ms *= world
+        else:
+            sum_d = levels_sum(t.blob, t.off)
+            n_ids, visited, n_walked = st["n_ids"], st["visited"], n
+        walk_bytes = 8 * sum_d + 32 * visited + 4 * (n_ids + n_walked)
+        achieved = walk_bytes / (walk_ms * 1e-3) / 1e9
+        path_bytes = (nbytes + 4 * n) + 16 * sum_d + 32 * visited + 4 * (n_ids + n)
 
     traffic = walk_traffic(args.config, f.n, n) if (args.mode == "replicate" and world == 1) else None
     host = None
-    if _host_leg(args, world, shard):
+    if full and _host_leg(args, world, shard):
         log("[rank 0] timing the host-visible path ...")
         host = host_e2e(gm, t, mode)
         log("[rank 0] timing the batcher's operating points ...")
         host["batcher"] = host_batcher_curve(gm, t, mode)
     if rank == 0:
         cpu = None
-        if args.cpu_baseline == "auto" and world == 1 and f.n > 20_000_000:
+        cpu_leg = full and args.cpu_baseline == "auto" and world == 1
+        if cpu_leg and f.n > 20_000_000:
             log("[rank 0] CPU baseline skipped: the string-keyed oracle table does not fit this host at "
                 f"{f.n} filters")
-        elif args.cpu_baseline == "auto" and world == 1:
+        elif cpu_leg:
             log("[rank 0] timing the CPU baseline ...")
             cpu = cpu_baseline(f, t, mode, args.cpu_seconds)
         line = {
@@ -916,7 +1017,7 @@ def main():
                        "rows": ("walk order + row -> topic map (egm_match_device_ordered)" if bufs["walk_rows"]
                                 else "input order (egm_match_device)")},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
+                         "frac": achieved / HBM_PEAK_GBS if achieved is not None else None,
                          "traffic": traffic[0]["traffic_bytes_per_launch"] if traffic else None,
                          "traffic_source": traffic[1] if traffic else None,
                          # the counters' bytes over the same time (beside, not instead of,
@@ -927,7 +1028,8 @@ def main():
                          "kernel_src_sha": kernel_src_sha(),
                          "kernel_ms_isolated": iso_ms,
                          "frac_isolated": (walk_bytes / (iso_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if iso_ms else None,
-                         "path_frac": path_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
+                         "path_frac": (path_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS
+                                       if path_bytes is not None else None)},
             "stats": {"ids_per_step": n_ids, "visited_per_step": visited, "levels_per_step": sum_d,
                       "merged_ids_per_step": merged_ids,
                       "deferred_chunks": st["deferred_chunks"], "walk_iters": wc["iters"],

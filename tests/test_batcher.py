@@ -15,7 +15,11 @@ def test_size_and_linger_flush():
         return [x * 2 for x in items]
 
     b = Batcher(commit, batch_size=8, linger_ms=20)
-    futs = [b.push(i) for i in range(8)]
+    # the eight pushes under the batcher's own (re-entrant) lock: the flusher sees them
+    # all at once, however long this thread is held up between two pushes (a stall
+    # of more than the linger there made the first batch a linger flush of fewer)
+    with b._cv:
+        futs = [b.push(i) for i in range(8)]
     assert [f.result(timeout=2) for f in futs] == [i * 2 for i in range(8)]
     t0 = time.monotonic()
     f = b.push(100)
