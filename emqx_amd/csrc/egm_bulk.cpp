@@ -4,9 +4,10 @@
 // first occurrence of a repeated filter wins) followed by relayout():
 //
 //   * word ids in order of first occurrence (filter order, then word order);
-//   * nodes numbered breadth-first, a parent's children in the order the
+//   * nodes ranked breadth-first, a parent's children in the order the
 //     filters first reach them (what relayout's BFS over creation-ordered
-//     node ids gives);
+//     node ids gives), then numbered as relayout numbers them: the '+'
+//     children 1..P in rank order, the other nodes from P+1 in rank order;
 //   * ref-counts, '+'/'#' children, '#' and terminal filter ids, literal-child
 //     signatures and flags exactly as insert + relayout set them;
 //   * the edge table at relayout's size, edges inserted in child order (a
@@ -27,6 +28,7 @@
 #include <algorithm>
 #include <string_view>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -401,6 +403,54 @@ int HostTable::bulk_build(const uint8_t* blob, const uint32_t* off, uint32_t n, 
   std::vector<uint32_t>().swap(cur_node);
   std::vector<uint32_t>().swap(tok);
   const uint32_t N = (uint32_t)nn.size();
+  // ---- 3b. the node layout (egm_common.h NODE_LAYOUT_VERSION), as relayout ----
+  // Ids so far are BFS ranks.  One stable partition of ranks 1..N-1 gives the
+  // '+' children ids 1..P and the literal and '#' children P+1.., each class
+  // in rank order: per-part counts, a scan over the parts, one scatter per
+  // array.  Literal children keep their relative order, so step 4 still
+  // inserts the edges in BFS rank of the child.
+  if (N > 1) {
+    std::vector<uint32_t> pbase(nt + 1, 0);   // '+' children before part t
+    parallel_for(N, nt, [&](size_t lo, size_t hi, unsigned t) {
+      uint32_t k = 0;
+      for (size_t c = lo; c < hi; ++c) k += nvia[c] == WID_PLUS;
+      pbase[t + 1] = k;
+    });
+    for (unsigned t = 0; t < nt; ++t) pbase[t + 1] += pbase[t];
+    const uint32_t P = pbase[nt];
+    if (P) {
+      std::vector<uint32_t> newid(N);
+      parallel_for(N, nt, [&](size_t lo, size_t hi, unsigned t) {
+        uint32_t np = 1 + pbase[t], no = P + 1 + (lo ? (uint32_t)lo - 1 - pbase[t] : 0u);
+        for (size_t c = lo; c < hi; ++c) newid[c] = c == 0 ? 0u : nvia[c] == WID_PLUS ? np++ : no++;
+      });
+      const size_t room = N + N / 8 + 1024;
+      auto remap = [&](uint32_t x) { return x == NONE ? NONE : newid[x]; };
+      // v scattered into out; out is left holding v's old memory (the u32
+      // arrays pass one spare along, so only the first of them touches new pages)
+      auto permute = [&](auto& v, auto& out, auto fix) {
+        out.reserve(room);
+        out.resize(N);
+        parallel_for(N, nt, [&](size_t lo, size_t hi, unsigned) {
+          for (size_t c = lo; c < hi; ++c) out[newid[c]] = fix(v[c]);
+        });
+        v.swap(out);
+      };
+      {
+        std::vector<NodeRec> spare;
+        permute(nn, spare, [&](NodeRec r) {
+          r.plus_child = remap(r.plus_child);
+          return r;
+        });
+      }
+      std::vector<uint32_t> spare;
+      permute(nhc, spare, remap);
+      permute(npar, spare, remap);
+      permute(nvia, spare, [](uint32_t x) { return x; });
+      permute(nref, spare, [](uint32_t x) { return x; });
+    }
+  }
+  phase("node layout");
   nodes.swap(nn);
   hash_child.swap(nhc);
   parent_.swap(npar);

@@ -76,6 +76,19 @@ static_assert(EDGE_BUCKET == 2 || EDGE_BUCKET == 4, "a bucket is one or two 64-B
 // costs the walking wave a second dependent round trip.
 constexpr uint32_t EDGE_SPREAD = EGM_EDGE_SPREAD;
 
+// Node ids.  The root is node 0.  A walker reads nodes[] only at the root and
+// at '+' children (a literal child's record travels in its edge slot, a '#'
+// child's filter id sits in its parent's record), so relayout() and the bulk
+// build give the P nodes reached by a '+' word the ids 1..P, in the order a
+// breadth-first walk from the root meets them, and every other node an id
+// from P+1, in that same order among themselves: the records a walk can want
+// are packed four to a 64-B line, the upper levels' first, '+' children of
+// neighbouring parents side by side.  Nodes inserted after a layout are
+// appended (or reuse a freed id) and stay outside the dense region until the
+// next relayout or bulk build; nothing but locality depends on the numbering.
+// The number of this node-id layout (1: plain BFS order; 2: '+' children first):
+constexpr uint32_t NODE_LAYOUT_VERSION = 2;
+
 struct NodeRec {          // 16 B, one dwordx4 load
   uint32_t plus_child;    // node reached by '+', or NONE
   uint32_t hash_fid;      // filter id of "P/#", or NONE

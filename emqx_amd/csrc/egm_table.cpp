@@ -476,9 +476,16 @@ int HostTable::remove(const uint8_t* p, uint32_t len) {
   return 0;
 }
 
-// Renumber live nodes breadth-first from the root so that every level is a
-// contiguous id range (the hot upper levels then share cache lines), and
-// rebuild the edge table at <= 25 % load.
+// Renumber live nodes in the layout of egm_common.h (NODE_LAYOUT_VERSION) and
+// rebuild the edge table at <= 25 % load.  A breadth-first walk from the root
+// (a parent's children in id order, which on a freshly inserted table is the
+// order they were created in) ranks the nodes; the root stays 0, the '+'
+// children take ids 1..P in rank order — the only records besides the root's
+// that a walker reads from nodes[], packed four to a 64-B line, the hot upper
+// levels' first and the '+' children of consecutive parents side by side —
+// and the literal and '#' children follow from P + 1 in rank order.  Nodes
+// inserted afterwards are appended (or reuse a freed id), so a new '+' child
+// sits outside the dense region until the next relayout or bulk build.
 void HostTable::relayout() {
   dirty_.nodes_full = dirty_.edges_full = true;   // every node id changes
   std::vector<uint32_t>().swap(dirty_.nodes);
@@ -495,20 +502,32 @@ void HostTable::relayout() {
     for (uint32_t n = 1; n < N; ++n)
       if (parent_[n] != NONE) kids[pos[parent_[n]]++] = n;
   }
-  std::vector<uint32_t> order;
-  order.reserve(n_live_nodes_);
-  std::vector<uint32_t> newid(N, NONE);
-  order.push_back(0);
-  newid[0] = 0;
-  for (size_t qi = 0; qi < order.size(); ++qi) {
-    uint32_t n = order[qi];
+  std::vector<uint32_t> bfs;
+  bfs.reserve(n_live_nodes_);
+  bfs.push_back(0);
+  uint32_t P = 0;   // '+' children
+  for (size_t qi = 0; qi < bfs.size(); ++qi) {
+    uint32_t n = bfs[qi];
     for (uint32_t k = cnt[n]; k < cnt[n + 1]; ++k) {
-      uint32_t c = kids[k];
-      newid[c] = (uint32_t)order.size();
-      order.push_back(c);
+      bfs.push_back(kids[k]);
+      P += via_[kids[k]] == WID_PLUS;
     }
   }
-  const uint32_t L = (uint32_t)order.size();
+  const uint32_t L = (uint32_t)bfs.size();
+  // order[new id] = old id: the root, the '+' children, the rest, each class in BFS rank
+  std::vector<uint32_t> order(L);
+  std::vector<uint32_t> newid(N, NONE);
+  {
+    uint32_t np = 1, no = P + 1;
+    for (uint32_t i = 1; i < L; ++i) {
+      const uint32_t o = bfs[i], id = via_[o] == WID_PLUS ? np++ : no++;
+      order[id] = o;
+      newid[o] = id;
+    }
+    order[0] = 0;
+    newid[0] = 0;
+  }
+  std::vector<uint32_t>().swap(bfs);
   std::vector<NodeRec> nn(L);
   std::vector<uint32_t> nhc(L), npar(L), nvia(L), nref(L), nlit(L);
   for (uint32_t i = 0; i < L; ++i) {
@@ -546,6 +565,7 @@ void HostTable::relayout() {
   edges.assign(nb * EDGE_BUCKET, EdgeSlot{NONE, 0, 0, 0, NONE, NONE, NONE, 0});
   n_edges_ = n_edge_tombs_ = 0;
   // insert in BFS order of the child so that bucket contents follow the levels
+  // (literal children keep their BFS rank order among themselves, so their id order is it)
   std::vector<EdgeSlot> live;
   live.reserve(old.size());
   for (const EdgeSlot& s : old)

@@ -74,7 +74,7 @@ class HostTable {
   // whether a live filter holds this id
   bool id_in_use(uint32_t fid) const;
 
-  void relayout();          // BFS renumbering of nodes + edge table rebuild
+  void relayout();          // renumbering of nodes ('+' children first, each class in BFS order) + edge table rebuild
   void clear();
   // clear() + insert() of every filter + relayout(), in parallel (egm_bulk.cpp):
   // ids must be valid and unique, none NONE (validated by the caller).
