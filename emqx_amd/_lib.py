@@ -109,6 +109,7 @@ SIGNATURES = {
                                                    C.c_uint64]),
     "egm_last_stats": (C.c_int, [_P, _u64p, _u64p, _u32p, _u32p, _u32p]),
     "egm_last_guard": (C.c_int, [_P, _u32p]),
+    "egm_last_walk_chunks": (C.c_int, [_P, _u32p, _u32p]),
     "egm_last_walk_counters": (C.c_int, [_P, _u64p, _u64p, _u64p, _u64p, _u64p]),
     "egm_last_walk_probes": (C.c_int, [_P, _u64p, _u64p]),
     "egm_set_timing": (C.c_int, [_P, C.c_int]),

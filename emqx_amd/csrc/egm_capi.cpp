@@ -1186,6 +1186,16 @@ int egm_last_stats(egm_ctx* c, uint64_t* n_ids, uint64_t* visited, uint32_t* n_d
   return EGM_OK;
 }
 
+int egm_last_walk_chunks(egm_ctx* c, uint32_t* deep, uint32_t* deferred) {
+  if (!c) return EGM_E_INVAL;
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  int r = sync_last(c);
+  if (r) return r;
+  if (deep) *deep = c->last.n_deep;
+  if (deferred) *deferred = c->last.n_deferred;
+  return EGM_OK;
+}
+
 int egm_last_guard(egm_ctx* c, uint32_t* guard) {
   if (!c || !guard) return EGM_E_INVAL;
   std::lock_guard<std::recursive_mutex> g(c->mu);

@@ -279,6 +279,12 @@ class GpuMatcher:
         self._check(self.lib.egm_last_guard(self.ctx, C.byref(g)), "egm_last_guard")
         return g.value
 
+    def walk_chunks(self) -> dict:
+        """Chunks of the last batch walked by the deep pass / deferred to the heavy kernel."""
+        a, b = C.c_uint32(), C.c_uint32()
+        self._check(self.lib.egm_last_walk_chunks(self.ctx, C.byref(a), C.byref(b)), "egm_last_walk_chunks")
+        return {"deep": a.value, "deferred": b.value}
+
     def walk_counters(self) -> dict:
         a, b, c, d, e = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self.lib.egm_last_walk_counters(self.ctx, C.byref(a), C.byref(b), C.byref(c), C.byref(d),

@@ -257,6 +257,11 @@ int egm_last_stats(egm_ctx* ctx, uint64_t* n_ids, uint64_t* visited, uint32_t* n
    overrun (impossible by the pop bound: a bug), 8 = a walk loop ran past its
    iteration guard (reported instead of hanging the GPU). */
 int egm_last_guard(egm_ctx* ctx, uint32_t* guard);
+/* Which kernel walked the last batch's chunks: those the first pass handed
+   to the deep pass (a topic of more than 12 levels) and those deferred whole
+   to the heavy kernel (a topic of more than 440 levels, or the force-heavy
+   test hook).  Read-only counters; either pointer may be NULL. */
+int egm_last_walk_chunks(egm_ctx* ctx, uint32_t* deep, uint32_t* deferred);
 /* Instrumentation: walk iterations and items popped of the last batch (lane
    occupancy = popped / (iters*64)), the iterations whose pop the stack-room
    bound cut short (the depth-first regime of deep, wide frontiers), and the
