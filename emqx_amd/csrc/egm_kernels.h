@@ -53,7 +53,7 @@ struct MatchStats {               // device-side counters, zeroed per batch
 // a counter bumped per flush would serialise across the 8 XCDs) and always
 // keeps REC_HDR u32 free at a segment's end: when the next record does not
 // fit it writes a jump {REC_JUMP, 0, target lo, target hi} there, so a chunk's
-// records are a chain from its first one (ChunkRec).  k_rec_rows then moves
+// records are a chain from its first one (ChunkRec).  k_rec_burst then moves
 // each chunk's ids into the rows, whose starts the scan of the counts gives.
 constexpr uint32_t REC_HDR = 4;
 constexpr uint32_t REC_IDS = REC_HDR + 32;        // u32 before the ids

@@ -489,29 +489,8 @@ constexpr uint32_t LEVEL_MAX = (1u << ML_BITS) - 1;
 #ifndef EGM_WALK_STAGE_DEEP
 #define EGM_WALK_STAGE_DEEP 320   // the deep pass's stage (LDS-bound: 448 would cost it a wave per CU)
 #endif
-#ifndef EGM_WALK_PAIRS
-#define EGM_WALK_PAIRS 0     // A/B: the first pass pops two items per lane per iteration
-#endif
-#ifndef EGM_PROBE_CONT
-#define EGM_PROBE_CONT 1     // a literal probe whose first line holds other keys is continued as a stack item
-                             // (1: the first pass; 2: both passes; 0: off — A/B)
-#endif
-#ifndef EGM_PROBE4
-#define EGM_PROBE4 0         // A/B: a literal probe reads all four slots of its bucket (two lines) at once
-#endif
-#ifndef EGM_PLUS_SKIP
-#define EGM_PLUS_SKIP 1      // skip a literal child's '+' transition that would do nothing (A/B: 0)
-#endif
 #ifndef EGM_WALK_WORDS
 #define EGM_WALK_WORDS 448   // staged topic word ids per wave (a chunk's topics, [topic][level])
-#endif
-#ifndef EGM_WALK_ITEM12
-#define EGM_WALK_ITEM12 0        // the first pass keeps 12 B per stack item (A/B)
-#endif
-#ifndef EGM_WALK_ITEM12_DEEP
-#define EGM_WALK_ITEM12_DEEP 1   // the deep pass keeps 12 B per stack item, the word re-read from the word stage:
-                                 // 504 items in 10 240 B, 16 waves per CU instead of 14 at 16 B x 448 (C3 deep
-                                 // walk 48.8 -> 45.4 ms, profiles/r6_walk_deep_item12_ab.jsonl)
 #endif
 #ifndef EGM_WALK_WORDS_DEEP
 #define EGM_WALK_WORDS_DEEP 448   // the deep pass's word stage (sub-chunks of S topics, S * dmax <= it)
@@ -569,16 +548,10 @@ struct RecCursor {
   uint32_t roff;                   // per lane: lane r holds the chunk's record r (offset / 4; r < REC_DIR)
 };
 
-#ifndef EGM_FLUSH_NT
-#define EGM_FLUSH_NT 1   // flush stores with the nontemporal hint: the records do not displace table lines from L2
-#endif
-__device__ __forceinline__ void st_u32(uint32_t* p, uint32_t v) {
-#if EGM_FLUSH_NT
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
+// Flush stores carry the nontemporal hint: the records do not displace table
+// lines from L2 (k_walk 9.62 against 9.78 ms with plain stores, round 4,
+// profiles/r4_walk_ab.jsonl; the plain-store switch was last present at aa0b013).
+__device__ __forceinline__ void st_u32(uint32_t* p, uint32_t v) { __builtin_nontemporal_store(v, p); }
 
 // Write the stage out as one flush record (round 5).  Each staged entry is
 // ranked inside its topic by an LDS atomic on the topic's flush counter
@@ -644,9 +617,6 @@ __device__ __forceinline__ void flush_stage(LDS& L, uint32_t nstage, uint32_t la
       if (j < REC_HDR) v = j == 0 ? (nstage | REC_TAG) : 0u;
       else if (j < REC_IDS) v = lo | (hi << 16);
       else v = j - REC_IDS < nstage ? L.stage_fid[j - REC_IDS] : 0u;
-#ifdef EGM_AB_NO_ID_STORES   // measurement only (tools/build_variant.py): the walk without its id stores
-      if (v != 0x7FFFFFF1u) continue;
-#endif
       st_u32(out + j, v);
     }
   }
@@ -681,10 +651,9 @@ __device__ __forceinline__ bool edge_probe_from(const DevTable& tab, uint32_t b,
 // the next word's literal-child signature bit with two VALU instead of
 // re-hashing the word (fmix64: ~13 VALU, five of them quarter-rate
 // multiplies, on every pop).  The reserved ids (WID_NONE/PLUS/HASH, >=
-// WID_MAX) keep their top bits (31), which no packed id has (< 28).
-#ifndef EGM_WORD_SIG
-#define EGM_WORD_SIG 1
-#endif
+// WID_MAX) keep their top bits (31), which no packed id has (< 28).  The host
+// decides per table (tab.sig_packed); the compile-time switch that forced the
+// re-hash (round 3's words) was last present at aa0b013.
 constexpr uint32_t WP_SHIFT = 27;
 __device__ __forceinline__ uint32_t word_pack(uint32_t w) {
   return w >= WID_MAX ? w : (w | (sig_index(w) << WP_SHIFT));
@@ -703,9 +672,6 @@ struct Pend {
   bool act, lit, plus, d1;  // d1: a one-word '$' topic (do_match/1's lookup_topic probe)
   uint4 prec, l0, h0, l1, h1;
   uint32_t line;            // the 64-B edge line read (its two slots are l0/h0, l1/h1)
-#if EGM_PROBE4
-  uint4 l2, h2, l3, h3;     // A/B: the bucket's second line (slots 2-3) read in the same round
-#endif
 };
 
 // Branch-free on purpose: every lane issues its loads unconditionally (an
@@ -731,12 +697,6 @@ __device__ __forceinline__ void issue(const DevTable& tab, const uint32_t* words
   p.h0 = ld16(bp + 16);
   p.l1 = ld16(bp + 32);
   p.h1 = ld16(bp + 48);
-#if EGM_PROBE4
-  p.l2 = ld16(bp + 64);
-  p.h2 = ld16(bp + 80);
-  p.l3 = ld16(bp + 96);
-  p.h3 = ld16(bp + 112);
-#endif
   // the next level's word (used only if level + 1 < D).  From the LDS stage
   // it is read unclamped, so the read does not wait for the topic's depth
   // (a leaf reads the next topic's word 0, or the pad word past the stage).
@@ -744,14 +704,12 @@ __device__ __forceinline__ void issue(const DevTable& tab, const uint32_t* words
   if (words) {
     const uint32_t raw = words[(meta & LEVEL_MAX) + 1];
     const uint32_t raw2 = words[(meta & LEVEL_MAX) + 2];
-#if EGM_WORD_SIG
     if (tab.sig_packed) {
       p.nw = word_plain(raw);
       p.nsig = word_sig(raw);
       p.nsig2 = word_sig(raw2);
       return;
     }
-#endif
     p.nw = raw;
     w2 = raw2;
   } else {
@@ -800,26 +758,11 @@ __device__ __forceinline__ void finish(const DevTable& tab, int mode, const Pend
   uint32_t hx = (p.h0.x & ~s1) | (p.h1.x & s1), hy = (p.h0.y & ~s1) | (p.h1.y & s1);
   uint32_t hz = (p.h0.z & ~s1) | (p.h1.z & s1), hw = (p.h0.w & ~s1) | (p.h1.w & s1);
   bool found = p.lit && (m0 || m1);
-#if EGM_PROBE4
-  const bool q = !m0 && !z0 && !m1 && !z1;   // slots 2-3 (already loaded) are next
-  const bool m2 = q && p.l2.x == node && p.l2.y == p.it.w, z2 = p.l2.x == NONE;
-  const bool m3 = q && !m2 && !z2 && p.l3.x == node && p.l3.y == p.it.w, z3 = p.l3.x == NONE;
-  {
-    const uint32_t s2 = m2 ? 0xFFFFFFFFu : 0u, s3 = m3 ? 0xFFFFFFFFu : 0u, k = s2 | s3;
-    cz = (cz & ~k) | (p.l2.z & s2) | (p.l3.z & s3);
-    cw = (cw & ~k) | (p.l2.w & s2) | (p.l3.w & s3);
-    hx = (hx & ~k) | (p.h2.x & s2) | (p.h3.x & s3);
-    hy = (hy & ~k) | (p.h2.y & s2) | (p.h3.y & s3);
-    hz = (hz & ~k) | (p.h2.z & s2) | (p.h3.z & s3);
-    hw = (hw & ~k) | (p.h2.w & s2) | (p.h3.w & s3);
-  }
-  found = found || (p.lit && (m2 || m3));
-  const bool slow = p.lit && q && !m2 && !z2 && !m3 && !z3;
-  constexpr int K0 = 4;
-#else
+  // (reading the bucket's second line in the same round, four slots per probe,
+  // measured 7.10 ms against 6.29 with twice the requests: round 6,
+  // profiles/r6_walk_probe_cont_ab.jsonl; last present at aa0b013)
   const bool slow = p.lit && !m0 && !z0 && !m1 && !z1;
   constexpr int K0 = 2;
-#endif
   o.slow = slow;
   if (!CONT && slow) {   // the slots read hold other keys: keep probing
     uint4 lo, hi;
@@ -840,15 +783,13 @@ __device__ __forceinline__ void finish(const DevTable& tab, int mode, const Pend
   // when the child is popped: if it would emit nothing and push nothing
   // there, the child does not take that transition — no record read, and no
   // pop at all for a child left with none — and it is counted as created
-  // here (SURVEY §8d V_t counts it)
+  // here (SURVEY §8d V_t counts it).  Round 5, profiles/r5_plus_skip_ab.jsonl:
+  // C2 k_walk 8.63 ms without the skip, 8.36 with it (383.1 M -> 363.2 M '+'
+  // reads); the form that always takes the transition was last present at aa0b013
   const uint32_t pfl = found ? hw : 0u;
   const bool leaf2 = level + 2 == D;
-#if EGM_PLUS_SKIP
   const bool puse = (pfl & F_HASH) || (leaf2 ? (pfl & F_TERM) != 0
                                             : ((pfl & F_PLUS) || ((pfl & p.nsig2) && (pfl & F_LIT))));
-#else
-  const bool puse = true;
-#endif
   const bool pskip = !leaf && (cw & F_PLUS) && !puse;
   const uint32_t go0 = (puse ? (cw & F_PLUS) : 0u) | ((cw & nsig) ? (cw & F_LIT) : 0u);
   o.p0 = !leaf && go0;
@@ -915,17 +856,30 @@ __device__ __forceinline__ const uint32_t* topic_words(const MatchWork& w, uint3
 // 64 roots at a time while the stack is short, and the wave pops up to 64
 // items per iteration.
 //
-// Two passes: the first (DEEP = false, a 320-item stack, 17 waves per CU)
-// walks the chunks of up to DEEP_MIN levels and hands deeper ones to the
-// second (DEEP = true: a 504-item stack of 12-B items, 16 waves per CU), whose wider stack
-// keeps the wave's pops full on deep, wide frontiers (C3: lane occupancy 0.39
-// -> 0.80) where the first pass's room bound would narrow it; a chunk deeper
-// than the deep pass takes goes to k_heavy.
-#ifdef EGM_WALK_WPE   // A/B: ask the compiler for this many waves per SIMD (caps VGPRs)
-#define EGM_WALK_ATTR __attribute__((amdgpu_waves_per_eu(EGM_WALK_WPE)))
-#else
-#define EGM_WALK_ATTR
-#endif
+// Two passes: the first (DEEP = false, a 320-item stack of 16-B items, 16
+// waves per CU: four per SIMD by its 105 VGPRs, and 10 112 B of LDS fit 16
+// too, see EGM_WALK_STAGE) walks the chunks of up to DEEP_MIN levels and hands
+// deeper ones to the second (DEEP = true: a 504-item stack of 12-B items, 16
+// waves per CU), whose wider stack keeps the wave's pops full on deep, wide
+// frontiers (C3: lane occupancy 0.39 -> 0.80) where the first pass's room
+// bound would narrow it; a chunk deeper than the deep pass takes goes to
+// k_heavy.
+//
+// Forms measured and retired (code last present at aa0b013; DESIGN §4.1.2,
+// §4.1.5, §4.1.7 hold the tables):
+//   two pops per lane in the first pass (up to 128 items per iteration, 138-142
+//     VGPRs -> 3 waves per SIMD): 12.29 against 9.62 ms in round 4
+//     (profiles/r4_walk_ab.jsonl), 7.77 against 5.80-5.87 ms in round 6 with
+//     12 % fewer iterations (profiles/r6_walk_probe_cont_ab.jsonl)
+//   12-B items in the first pass: 10.28 against 10.17 ms in round 3
+//     (profiles/r3_walk_ab.json), 5.92-5.94 against 5.86 ms in round 6: more
+//     waves per CU do not help a request-bound walk; 16-B items in the deep
+//     pass: 448 items, 14 waves per CU, C3 deep walk 48.8 against 45.4 ms
+//     (profiles/r6_walk_deep_item12_ab.jsonl)
+//   VGPRs capped for more waves per SIMD (amdgpu_waves_per_eu): 96 VGPRs for 17
+//     waves per CU spilled 20 B, 6.09 against 5.80-5.87 ms
+//     (profiles/r6_walk_probe_cont_ab.jsonl)
+
 // Hand the first n (wave-uniform) of lane-held chunk ids to the deep pass.
 __device__ __forceinline__ void deep_flush(const MatchWork& w, uint32_t c, uint32_t n, uint32_t lane) {
   uint32_t base = 0;
@@ -935,16 +889,22 @@ __device__ __forceinline__ void deep_flush(const MatchWork& w, uint32_t c, uint3
 }
 
 template <bool DEEP>
-__global__ __launch_bounds__(64) EGM_WALK_ATTR void k_walk(DevTable tab, const uint32_t* __restrict__ off, uint32_t n,
-                                                           int mode, MatchWork w) {
+__global__ __launch_bounds__(64) void k_walk(DevTable tab, const uint32_t* __restrict__ off, uint32_t n, int mode,
+                                             MatchWork w) {
   constexpr uint32_t STK = DEEP ? WALK_STACK_DEEP : WALK_STACK;
-  // probe continuations in the first pass only: the deep pass (C3) measured
-  // 53.8 -> 55.2 ms with them, the first pass (C2) 8.20 -> 6.23 ms (round 6)
-  constexpr bool PROBE_CONT = EGM_PROBE_CONT != 0 && (!DEEP || EGM_PROBE_CONT > 1);
+  // probe continuations (a literal probe whose first line holds other keys
+  // is continued as a stack item) in the first pass only: the deep pass (C3)
+  // measured 53.8 -> 55.2 ms with them (48.85 -> 48.83 with line-sized
+  // buckets, profiles/r6_walk_probe_cont_ab.jsonl), the first pass (C2) 8.20
+  // -> 6.23 ms (round 6; the switch for both passes or neither
+  // was last present at aa0b013)
+  constexpr bool PROBE_CONT = !DEEP;
   constexpr uint32_t STG = DEEP ? WALK_STAGE_DEEP : WALK_STAGE;
   constexpr uint32_t WRD = DEEP ? WALK_WORDS_DEEP : WALK_WORDS;
-  // (a continued probe keeps its line in z and its word is the one at its level: it fits 12 B too)
-  constexpr bool N12 = DEEP ? EGM_WALK_ITEM12_DEEP != 0 : EGM_WALK_ITEM12 != 0;
+  // the deep pass keeps 12 B per stack item, the word re-read from the word
+  // stage: 504 items in 10 240 B, 16 waves per CU; the first pass keeps 16 B
+  // (a continued probe keeps its line in z and its word is the one at its level: it would fit 12 B too)
+  constexpr bool N12 = DEEP;
   __shared__ WaveLds<STK, STG, WRD, N12> L;
   auto st_put = [&](uint32_t i, const uint4& v) {
     if constexpr (N12) {
@@ -1041,7 +1001,7 @@ __global__ __launch_bounds__(64) EGM_WALK_ATTR void k_walk(DevTable tab, const u
         const uint32_t j = sub + lane, Dj = L.tinfo[j] & 0xFFFFFFu;
         const uint32_t* src = topic_words(w, L.tinfo[j], gsub);
         uint32_t* dst = L.words + lane * dmax;
-        const bool pk = EGM_WORD_SIG && tab.sig_packed;
+        const bool pk = tab.sig_packed;
         uint32_t i = 0;
         for (; i + 4 <= Dj; i += 4) {
           const uint32_t a0 = src[i], a1 = src[i + 1], a2 = src[i + 2], a3 = src[i + 3];
@@ -1084,7 +1044,7 @@ __global__ __launch_bounds__(64) EGM_WALK_ATTR void k_walk(DevTable tab, const u
               fid = root.y;
               created += 1;
               const uint32_t w0r = L.words[(j & (S - 1)) * dmax];
-              const bool pk = EGM_WORD_SIG && tab.sig_packed;
+              const bool pk = tab.sig_packed;
               const uint32_t w0 = pk ? word_plain(w0r) : w0r;
               const uint32_t rf = root_flags(root, dollar, pk ? word_sig(w0r) : (w0 < WID_MAX ? sig_bit(w0) : 0u));
               has = rf != 0;
@@ -1117,22 +1077,13 @@ __global__ __launch_bounds__(64) EGM_WALK_ATTR void k_walk(DevTable tab, const u
         // narrows the wave instead.
         const uint32_t room = STK - sp;
         const uint32_t lim = room > dmax ? room - dmax : 1u;
-        // EGM_WALK_PAIRS (A/B): the first pass pops up to 128 items per
-        // iteration, two per lane — twice the reads in flight per wave and
-        // the iteration's fixed work shared by two items (same pop bound)
-        constexpr bool PAIRS = EGM_WALK_PAIRS && !DEEP;
-        const uint32_t want = min(PAIRS ? 128u : 64u, sp), take = min(want, lim), bi = sp - take;
-        const uint32_t take_a = min(take, 64u), take_b = take - take_a;
+        const uint32_t want = min(64u, sp), take = min(want, lim), bi = sp - take;
         bounded += take < want ? 1u : 0u;
         iters += 1;
         popped += take;
-        Pend p, pb;
-        p.act = lane < take_a;
+        Pend p;
+        p.act = lane < take;
         p.it = st_get(min(bi + lane, STK - 1));   // unconditional: see issue()
-        if (PAIRS) {
-          pb.act = lane < take_b;
-          pb.it = st_get(min(bi + 64 + lane, STK - 1));
-        }
         sp = bi;
         const uint32_t tt = (p.it.y >> MT_SHIFT) & 0x7Fu;
         const uint32_t ti = L.tinfo[tt];
@@ -1140,23 +1091,15 @@ __global__ __launch_bounds__(64) EGM_WALK_ATTR void k_walk(DevTable tab, const u
         p.d1 = p.D == 1 && ((ti >> 24) & TF_DOLLAR);   // TF_DOLLAR < 0x80: the fixed-stride bit is not read
         if constexpr (N12) {   // the item's word: its topic's staged word at its level
           const uint32_t raw = L.words[(tt & (S - 1)) * dmax + min(p.it.y & LEVEL_MAX, dmax - 1)];
-          p.it.w = (EGM_WORD_SIG && tab.sig_packed) ? word_plain(raw) : raw;
+          p.it.w = tab.sig_packed ? word_plain(raw) : raw;
         }
         issue<PROBE_CONT>(tab, L.words + (tt & (S - 1)) * dmax, nullptr, 0, p);
-        uint32_t ttb = 0;
-        if (PAIRS) {
-          ttb = (pb.it.y >> MT_SHIFT) & 0x7Fu;
-          const uint32_t tib = L.tinfo[ttb];
-          pb.D = tib & 0xFFFFFFu;
-          pb.d1 = pb.D == 1 && ((tib >> 24) & TF_DOLLAR);
-          issue<PROBE_CONT>(tab, L.words + (ttb & (S - 1)) * dmax, nullptr, 0, pb);
-          lit_probes += popc(__ballot(pb.lit));
-          plus_reads += popc(__ballot(pb.plus));
-        }
         lit_probes += popc(__ballot(p.lit));
         plus_reads += popc(__ballot(p.plus));
         wave_sync();
         // ---- consume: children -> stack, emits -> stage ----
+        // (a lambda with one caller: written inline, the same statements
+        // compile to different k_walk code, so it stays until the walk changes)
         auto consume = [&](const Pend& q, uint32_t qt) -> bool {
           Out o;
           finish<PROBE_CONT>(tab, mode, q, o);
@@ -1207,9 +1150,6 @@ __global__ __launch_bounds__(64) EGM_WALK_ATTR void k_walk(DevTable tab, const u
           return true;
         };
         if (!consume(p, tt)) break;
-        if (PAIRS && take_b) {
-          if (!consume(pb, ttb)) break;
-        }
         wave_sync();
       }
     }
@@ -1596,114 +1536,33 @@ __global__ __launch_bounds__(64 * COMPACT_WAVES) void k_compact(const uint4* __r
 // walk's record offsets, REC_DIR of them; a longer chunk continues along the
 // chain).  Each record is placed by scanning its 64 counts into the topics'
 // slots and storing every id at row start + the topic's running offset (its
-// owner found by a 6-step LDS search).  In walk-order rows a chunk's rows are
+// run found from a bitmap of run starts).  In walk-order rows a chunk's rows are
 // one contiguous run (and topic[k] is written here); in input order each
 // topic's piece of a record goes to a scattered row.  Chunks walked by k_heavy
 // are skipped (their ids arrive as pieces, k_compact).
 //
-// k_rec_rows (A/B, EGM_REC_ROWS=0) places one record at a time with the next
-// one's loads in flight; k_rec_burst (the default) loads REC_BURST records at
-// once.  Measured at C2 (r5, rocprof): 1.93 / 1.65 ms.  Two forms that
-// assemble the chunk in LDS first and store whole lines were slower: a 16 KB
-// LDS window per wave (4.2 ms: 9 waves per CU, a round trip per record) and
-// an in-order gather through an LDS table of the chunk's records (1.52 ms +
-// 0.37 ms for chunks of more than 16 records).  Stores of records as one
-// contiguous run (measurement only) take 0.93 ms and no stores 0.46 ms: the
-// runs of ~5 ids per topic and record are what costs.
+// k_rec_burst loads the chunk's records REC_BURST at a time from the
+// directory, all in one round, then places them one after the other — so a
+// chunk's output lines are written within a short burst and are completed in
+// L2 instead of being evicted half written.
+//
+// Forms measured and retired (C2, round 5, rocprof; DESIGN §4.1.3 holds the
+// table; the first was a second kernel in this file, last present at aa0b013):
+//   one record at a time with the next one's loads in flight: 1.93 against
+//     1.65 ms — each chunk stays open for ~11 dependent rounds, 4.1 GB written
+//     per batch for 1.99 GB of ids (PMC r5g; no profiles/ file holds this
+//     pair, profiles/r5_c2_final_kernel_stats.csv has the burst form's side);
+//     without its id stores (measurement only) 0.46 ms, with each record
+//     stored as one contiguous run (measurement only) 0.93 ms: the runs of ~5
+//     ids per topic and record are what costs
+//   the chunk assembled in a 16 KB LDS window per wave, whole lines stored:
+//     4.2 ms (9 waves per CU, a round trip per record)
+//   an in-order gather through an LDS table of the chunk's records: 1.52 ms +
+//     0.37 ms for chunks of more than 16 records
 constexpr int REC_WAVES = 4;
 constexpr uint32_t REC_IPL = (WALK_STAGE_MAX + 63) / 64;   // a record's ids, all loaded in one round
-struct RecLoad {
-  uint64_t off;
-  uint32_t hdr, cr;
-  uint32_t v[REC_IPL];
-};
-__global__ __launch_bounds__(64 * REC_WAVES) void k_rec_rows(const uint32_t* __restrict__ rec, uint64_t rec_cap,
-                                                             const uint4* __restrict__ chunks,
-                                                             const uint32_t* __restrict__ dir,
-                                                             const uint64_t* __restrict__ order, uint32_t n,
-                                                             const uint64_t* __restrict__ row_ptr,
-                                                             uint32_t* __restrict__ topic, uint32_t* __restrict__ ids,
-                                                             uint64_t ids_cap, MatchStats* stats, uint32_t ct) {
-  __shared__ uint32_t s_ex[REC_WAVES][64];
-  __shared__ uint64_t s_dst[REC_WAVES][64];
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const bool ok = compact_checks(row_ptr, n, ids_cap, stats);
-  const uint32_t nchunks = (n + ct - 1) / ct;
-  // every load of one record (out of the slab: header 0, which fails the tag check)
-  auto issue = [&](uint64_t o, RecLoad& L) {
-    const bool in = o + REC_IDS <= rec_cap;
-    const uint64_t oc = in ? o : 0ull;
-    L.off = o;
-    L.hdr = in ? rec[oc] : 0u;
-    L.cr = ((const uint16_t*)(rec + oc + REC_HDR))[lane];
-#pragma unroll
-    for (uint32_t k = 0; k < REC_IPL; ++k) L.v[k] = rec[min(oc + REC_IDS + lane + 64u * k, rec_cap - 1)];
-  };
-  for (uint32_t c = blockIdx.x * REC_WAVES + wave; c < nchunks; c += gridDim.x * REC_WAVES) {
-    const uint32_t t = c * ct + lane;
-    const bool act = lane < ct && t < n;
-    const uint32_t my_t = act ? (order ? (uint32_t)order[t] : t) : 0u;
-    if (topic && act) topic[t] = my_t;   // written even when the rows are not (overflow): the map is the order
-    const uint4 ch = chunks[c];
-    if (!ok || !(ch.w & CHUNK_WALKED) || ch.z == 0) continue;
-    const uint32_t nrec = ch.z;
-    uint64_t dst = act ? row_ptr[topic ? t : my_t] : 0ull;
-    const uint32_t roff = lane < min(nrec, REC_DIR) ? dir[(uint64_t)c * REC_DIR + lane] : 0u;
-    RecLoad A, B;
-    issue((uint64_t)ch.x | ((uint64_t)ch.y << 32), A);
-    for (uint32_t r = 0; r < nrec; ++r) {
-      const bool next_dir = r + 1 < nrec && r + 1 < REC_DIR;
-      if (next_dir) issue((uint64_t)(uint32_t)__shfl((int)roff, (int)(r + 1), 64) << 2, B);   // in flight now
-      uint32_t tot;
-      const uint32_t ex = wave_excl_scan(A.cr, lane, &tot);
-      if ((A.hdr & 0xFFFF0000u) != REC_TAG || (A.hdr & 0xFFFFu) != tot || tot > WALK_STAGE_MAX) {
-        if (lane == 0) atomicOr(&stats->guard, GUARD_STACK);   // a broken directory or chain: a bug, reported
-        break;
-      }
-      s_ex[wave][lane] = ex;
-      s_dst[wave][lane] = dst;
-      dst += A.cr;
-      wave_sync();
-#ifdef EGM_AB_REC_STORE   // measurement only: 0 = no id stores
-#pragma unroll
-      for (uint32_t k = 0; k < REC_IPL; ++k)
-        if (A.v[k] == 0x7FFFFFF1u) ids[0] = A.v[k];
-#else
-#pragma unroll
-      for (uint32_t k = 0; k < REC_IPL; ++k) {
-        const uint32_t q = lane + 64u * k;
-        if (q < tot) {
-          uint32_t o = 0;
-#pragma unroll
-          for (uint32_t step = 32; step >= 1; step >>= 1)
-            if (s_ex[wave][o + step] <= q) o += step;
-          ids[s_dst[wave][o] + (q - s_ex[wave][o])] = A.v[k];
-        }
-      }
-#endif
-      wave_sync();
-      if (r + 1 < nrec && !next_dir) {   // past the directory: the chain (rare: a chunk of > REC_DIR records)
-        uint64_t o = A.off + rec_size(tot);
-        if (o + REC_HDR <= rec_cap && (rec[o] & 0xFFFF0000u) == REC_JUMP)   // wave-uniform
-          o = (uint64_t)rec[o + 2] | ((uint64_t)rec[o + 3] << 32);
-        issue(o, B);
-      }
-      A = B;
-    }
-  }
-}
-
-// The burst form of k_rec_rows (round 5): the chunk's records are loaded
-// REC_BURST at a time from the directory, all in one round, then placed one
-// after the other — so a chunk's output lines are written within a short
-// burst and are completed in L2 instead of being evicted half written (the
-// direct form keeps each chunk open for ~11 dependent rounds: 4.1 GB written
-// per C2 batch for 1.99 GB of ids, PMC r5g).
 #ifndef EGM_REC_BURST
 #define EGM_REC_BURST 7   // a C2 chunk's ids come in ~7 records of 480 (burst 8 at 8 ids per lane spills 44 B)
-#endif
-#ifndef EGM_REC_BITMAP
-#define EGM_REC_BITMAP 1   // ids placed through a bitmap of run starts (A/B: 0, the LDS search)
 #endif
 #ifndef EGM_REC_WPE
 #define EGM_REC_WPE 4      // waves per SIMD k_rec_burst is compiled for (caps its VGPRs at 128)
@@ -1716,20 +1575,13 @@ __global__ __launch_bounds__(64 * REC_WAVES) __attribute__((amdgpu_waves_per_eu(
                                                               const uint64_t* __restrict__ row_ptr,
                                                               uint32_t* __restrict__ topic, uint32_t* __restrict__ ids,
                                                               uint64_t ids_cap, MatchStats* stats, uint32_t ct) {
-#if EGM_REC_BITMAP
   __shared__ uint64_t s_bm[REC_WAVES][REC_IPL];   // the record's run starts (bit q: an id position where a topic's run begins)
   __shared__ uint64_t s_dst[REC_WAVES][64];       // the r-th run: its topic's next id in HBM minus the run's start
-#else
-  __shared__ uint32_t s_ex[REC_WAVES][64];
-  __shared__ uint64_t s_dst[REC_WAVES][64];
-#endif
   const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const bool ok = compact_checks(row_ptr, n, ids_cap, stats);
-#if EGM_REC_BITMAP
   if (lane < REC_IPL) s_bm[wave][lane] = 0ull;
   wave_sync();
   const uint64_t lmask = (2ull << lane) - 1ull;   // positions <= lane of a 64-position word (lane 63: all)
-#endif
   const uint32_t nchunks = (n + ct - 1) / ct;
   for (uint32_t c = blockIdx.x * REC_WAVES + wave; c < nchunks; c += gridDim.x * REC_WAVES) {
     const uint32_t t = c * ct + lane;
@@ -1786,10 +1638,11 @@ __global__ __launch_bounds__(64 * REC_WAVES) __attribute__((amdgpu_waves_per_eu(
           break;
         }
         chain = off[b] + rec_size(tot);
-#if EGM_REC_BITMAP
         // round 6: each non-empty topic marks where its run starts; an id's run
         // is then the count of starts at or before it (popcounts of the bitmap)
-        // instead of a 6-step LDS search per id (k_rec_burst's VALU: 407M per C2 batch)
+        // instead of a 6-step LDS search per id over the records' scanned counts
+        // (1.83 against 1.91 ms, VALU 407 M -> 284 M per C2 batch,
+        // profiles/r6_rec_window_ab.jsonl; the search was last present at aa0b013)
         {
           const bool ne = cr[b] != 0;
           const uint64_t bal = __ballot(ne);
@@ -1813,24 +1666,6 @@ __global__ __launch_bounds__(64 * REC_WAVES) __attribute__((amdgpu_waves_per_eu(
           }
           wave_sync();
         }
-#else
-        s_ex[wave][lane] = ex;
-        s_dst[wave][lane] = dst;
-        dst += cr[b];
-        wave_sync();
-#pragma unroll
-        for (uint32_t k = 0; k < REC_IPL; ++k) {
-          const uint32_t q = lane + 64u * k;
-          if (q < tot) {
-            uint32_t o = 0;
-#pragma unroll
-            for (uint32_t step = 32; step >= 1; step >>= 1)
-              if (s_ex[wave][o + step] <= q) o += step;
-            ids[s_dst[wave][o] + (q - s_ex[wave][o])] = v[b][k];
-          }
-        }
-        wave_sync();
-#endif
       }
     }
   }
@@ -1850,10 +1685,9 @@ int walk_grid_blocks(uint32_t n) {
 // 12-B items, 14 at round 5's 448 16-B items).  A wave that does not fit would start only when another ends, with
 // a whole share of chunks still to walk: C3 measured 59 ms at 10 waves per CU
 // and 640 items, 80 ms when an 11th was asked for, 53 ms at 14 waves of 448
-// items (r5 A/B).  EGM_DEEP_WAVES forces a count (A/B).
-#ifndef EGM_DEEP_WAVES
-#define EGM_DEEP_WAVES 0   // 0: the occupancy the runtime reports for k_walk<true>
-#endif
+// items (r5 A/B, DESIGN §4.1.5, measured with a compile-time forced count
+// that was last present at aa0b013).  The count is the occupancy the runtime
+// reports for k_walk<true>.
 // The runtime's figure is capped by what the LDS holds at a 1280-B allocation
 // granule (160 KB / 128): round 6 measured the deep pass with waves of 11 600 B
 // (the runtime said 14 per CU, 12 fit) at 65.6 ms against 48.8 ms at 11 344 B
@@ -1863,13 +1697,10 @@ constexpr int LDS_PER_CU = 160 * 1024;
 constexpr int LDS_GRANULE = 1280;
 static uint32_t deep_waves_per_cu() {
   static const uint32_t v = [] {
-    int nb = EGM_DEEP_WAVES;
-    if (nb <= 0 &&
-        (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_walk<true>, 64, 0) != hipSuccess || nb <= 0))
-      nb = 8;
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_walk<true>, 64, 0) != hipSuccess || nb <= 0) nb = 8;
     hipFuncAttributes fa;
-    if (EGM_DEEP_WAVES <= 0 && hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_walk<true>)) == hipSuccess &&
-        fa.sharedSizeBytes > 0) {
+    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_walk<true>)) == hipSuccess && fa.sharedSizeBytes > 0) {
       const int per = (int)((fa.sharedSizeBytes + LDS_GRANULE - 1) / LDS_GRANULE) * LDS_GRANULE;
       nb = std::max(1, std::min(nb, LDS_PER_CU / per));
     }
@@ -1954,9 +1785,6 @@ uint32_t walk_key_bits(uint32_t shape) {
 constexpr int SORT_THREADS = 256;
 #ifndef EGM_SORT_ITEMS
 #define EGM_SORT_ITEMS 15                                       // pairs per thread: 3840 per tile, 51 KB LDS -> 3 blocks/CU
-#endif
-#ifndef EGM_SORT_TICKET
-#define EGM_SORT_TICKET 1                                       // 0 (A/B): tile = blockIdx (in-order dispatch assumed)
 #endif
 constexpr int SORT_ITEMS = EGM_SORT_ITEMS;
 constexpr uint32_t SORT_TILE = SORT_THREADS * SORT_ITEMS;
@@ -2048,11 +1876,10 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_pass(const uint32_t* __re
   __shared__ uint32_t s_wsum[SORT_THREADS / 64];
   __shared__ uint32_t s_tile;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#if EGM_SORT_TICKET
+  // the tile is a ticket, not blockIdx: dispatch order is not guaranteed across
+  // the eight XCDs and the look-back waits for earlier tiles (blockIdx tiles
+  // measured 0.075 against 0.087 ms per pass; last present at aa0b013)
   if (tid == 0) s_tile = atomicAdd(ticket, 1u);
-#else
-  if (tid == 0) s_tile = blockIdx.x;
-#endif
   for (uint32_t i = tid; i < (SORT_THREADS / 64) * 256; i += SORT_THREADS) (&s_cnt[0][0])[i] = 0;
   __syncthreads();
   const uint32_t tile = s_tile;
@@ -2151,17 +1978,11 @@ __global__ __launch_bounds__(SORT_THREADS) void k_sort_pass(const uint32_t* __re
   for (uint32_t j = tid; j < nt; j += SORT_THREADS) {
     const uint32_t kk = s_key[j];
     const uint32_t dg = (kk >> shift) & 0xFFu;
-#if defined(EGM_SORT_AB) && EGM_SORT_AB == 2   // measurement only: every tile's output contiguous (not a sort)
-    const uint64_t dst = base + j + (dg & 0u);
-#else
+    // (measurement-only forms, last present at aa0b013: a pass without these
+    // stores 0.075 ms, with every tile's output contiguous 0.080 ms, against 0.087)
     const uint64_t dst = (uint64_t)s_base[dg] + (j - s_start[dg]);
-#endif
-#if defined(EGM_SORT_AB) && EGM_SORT_AB == 1   // measurement only: no output stores
-    if (kk == 0x7FFFFFF1u && s_val[j] == 0x7FFFFFF1ull) vout[0] = dst;
-#else
     if (kout) kout[dst] = kk;
     vout[dst] = s_val[j];
-#endif
   }
 }
 
@@ -2257,19 +2078,11 @@ hipError_t launch_match(const DevTable& tab, const uint8_t* blob, const uint32_t
   // get a small grid (the piece count is only known on the device)
   const uint32_t cblocks =
       (uint32_t)std::min<uint64_t>(EGM_COMPACT_BLOCKS, std::max<uint64_t>(256, ((uint64_t)n + 63) / 64));
-#ifndef EGM_REC_ROWS
-#define EGM_REC_ROWS 1   // 1: k_rec_burst; 0: k_rec_rows (A/B)
-#endif
   const uint32_t rblocks = (uint32_t)std::min<uint64_t>(
       65536, std::max<uint64_t>(1, (((uint64_t)n + w.ct - 1) / w.ct + REC_WAVES - 1) / REC_WAVES));
-#if EGM_REC_ROWS
   hipLaunchKernelGGL(k_rec_burst, dim3(rblocks), dim3(64 * REC_WAVES), 0, s, w.rec, w.rec_cap, w.chunks, w.dir,
                      w.order, n, out.row_ptr, out.topic, out.ids, out.ids_cap, w.stats, w.ct);
-#else   // A/B: one record at a time, the next in flight
-  hipLaunchKernelGGL(k_rec_rows, dim3(rblocks), dim3(64 * REC_WAVES), 0, s, w.rec, w.rec_cap, w.chunks, w.dir,
-                     w.order, n, out.row_ptr, out.topic, out.ids, out.ids_cap, w.stats, w.ct);
-#endif
-  trace(s, "k_rec_rows");
+  trace(s, "k_rec_burst");
   hipLaunchKernelGGL(k_compact, dim3(cblocks), dim3(64 * COMPACT_WAVES), 0, s, w.pieces, w.ids_tmp, n, out.row_ptr,
                      out.ids, out.ids_cap, w.pieces_cap, w.stats);
   return hipGetLastError();

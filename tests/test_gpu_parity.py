@@ -206,7 +206,7 @@ def test_config_c0_heavy_path_vs_cpp_oracle(gm, mode):
 def test_walk_orders_vs_cpp_oracle(gm, mode, monkeypatch):
     """The walk's locality order (the key k_tokenise computes, the radix sort,
     the walk reading sorted topic records and fixed-stride words) and the
-    output path (flush records chained per chunk, k_rec_rows) never change a
+    output path (flush records chained per chunk, k_rec_burst) never change a
     result: several key shapes, input order, a partial last chunk, sorted +
     every chunk through k_heavy, and records of 1..40 entries in segments of
     64-100 u32 (every chunk's chain jumps between segments many times), all
