@@ -24,7 +24,12 @@ LIB = os.path.join(HERE, "libemqx_gpu_match.so")
 SYNTH = os.path.join(HERE, "libegm_synth.so")
 ORACLE = os.path.join(ROOT, "oracle", "liboracle_trie.so")
 
-HEADERS = [os.path.join(CSRC, f) for f in ("egm_common.h", "egm_table.h", "egm_kernels.h", "egm_dma.h", "egm_pack.h")] + [
+# the library's sources (tools/build_variant.py builds the same lists)
+HIP_SOURCES = ("egm_kernels.hip", "egm_pack.hip")
+HOST_SOURCES = ("egm_table.cpp", "egm_bulk.cpp", "egm_capi.cpp", "egm_match.cpp", "egm_pipe.cpp", "egm_fanout.cpp",
+                "egm_part.cpp", "egm_retain.cpp", "egm_dma.cpp")
+HEADERS = [os.path.join(CSRC, f) for f in ("egm_common.h", "egm_table.h", "egm_kernels.h", "egm_dma.h", "egm_pack.h",
+                                           "egm_alloc.h", "egm_buf.h", "egm_ctx.h")] + [
     os.path.join(ROOT, "include", "emqx_gpu_match.h")]
 
 
@@ -53,14 +58,14 @@ def _run(cmd, verbose):
 def build_lib(verbose=False, force=False) -> str:
     os.makedirs(BUILD, exist_ok=True)
     objs = []
-    for name in ("egm_kernels.hip", "egm_pack.hip"):
+    for name in HIP_SOURCES:
         hip_src = os.path.join(CSRC, name)
         o = os.path.join(BUILD, name.replace(".hip", ".o"))
         if force or _stale(o, [hip_src] + HEADERS):
             _run([_hipcc(), f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-result",
                   "-Wno-unused-value", "-c", hip_src, "-o", o], verbose)
         objs.append(o)
-    for name in ("egm_table.cpp", "egm_bulk.cpp", "egm_capi.cpp", "egm_retain.cpp", "egm_dma.cpp"):
+    for name in HOST_SOURCES:
         src = os.path.join(CSRC, name)
         o = os.path.join(BUILD, name.replace(".cpp", ".o"))
         if force or _stale(o, [src] + HEADERS):

@@ -28,42 +28,15 @@
 
 #include "../../include/emqx_gpu_match.h"
 #include "egm_alloc.h"
+#include "egm_buf.h"
 #include "egm_kernels.h"
 
 using namespace egm;
 
 namespace {
 
-struct Buf {
-  void* p = nullptr;
-  size_t cap = 0;
-  Buf() = default;
-  Buf(const Buf&) = delete;
-  Buf& operator=(const Buf&) = delete;
-  ~Buf() { release(); }
-  void release() {
-    if (p) hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap && p) return hipSuccess;
-    release();
-    size_t b = std::max<size_t>(bytes, 256);
-    hipError_t e = hipMalloc(&p, b);
-    if (e != hipSuccess) {
-      p = nullptr;
-      return e;
-    }
-    cap = b;
-    return hipSuccess;
-  }
-  template <class T>
-  T* as() const { return (T*)p; }
-};
-
 template <class T>
-hipError_t put_vec(Buf& b, const std::vector<T>& v) {
+hipError_t put_vec(DevBuf& b, const std::vector<T>& v) {
   hipError_t e = b.ensure(v.size() * sizeof(T) + 16);
   if (e == hipSuccess && !v.empty()) e = hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
   return e;
@@ -227,6 +200,9 @@ void build_image(const std::unordered_map<std::string, Rec>& recs, Image* im) {
 
 }  // namespace
 
+// (-Wattributes: the opaque egm_rstore is less hidden than DevBuf, as egm_ctx is; see egm_ctx.h)
+#pragma GCC diagnostic push
+#pragma GCC diagnostic ignored "-Wattributes"
 struct egm_rstore {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -235,12 +211,12 @@ struct egm_rstore {
   bool dirty = true;
   std::string err;
   // committed image
-  Buf nodes, edges, dict, dict_blob, dict_off, msg, expiry;
+  DevBuf nodes, edges, dict, dict_blob, dict_off, msg, expiry;
   RetainView view{};
   DevTable dtab{};
   uint64_t n_nodes = 0;
   // per-batch workspace
-  Buf in_blob, in_off, wid, lv, tfl, pf[2], pn[2], pc, paux, poff, tiles, rf, rlo, rhi, nr, alive, apre, fcnt, roff,
+  DevBuf in_blob, in_off, wid, lv, tfl, pf[2], pn[2], pc, paux, poff, tiles, rf, rlo, rhi, nr, alive, apre, fcnt, roff,
       row, ids;
 
   int fail(int code, const std::string& m) {
@@ -252,6 +228,7 @@ struct egm_rstore {
     return EGM_E_DEVICE;
   }
 };
+#pragma GCC diagnostic pop
 
 static int rs_commit_locked(egm_rstore* r) {
   if (!r->dirty) return EGM_OK;

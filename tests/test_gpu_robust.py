@@ -225,7 +225,7 @@ def test_pipeline_submit_wait(gm):
 
 def test_pipeline_deep_in_flight_exact(gm):
     """Round 4's copier thread (results moved by SDMA copies sized from the
-    device's id total, egm_capi.cpp copier_main): 4-6 batches in flight on a
+    device's id total, egm_pipe.cpp copier_main): 4-6 batches in flight on a
     fresh context — its first batches overflow their slots' id room and are
     rerun — of C2-shaped topics (~50 ids per topic), every result equal to the
     one-by-one device match, itself checked against the C++ oracle on a sample."""
