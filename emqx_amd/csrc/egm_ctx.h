@@ -114,6 +114,7 @@ struct MatchWs {
   uint64_t pieces_cap = 0, ids_tmp_cap = 0, rec_cap = 0;
   uint32_t rec_grain = REC_GRAIN, flush_lim = 0;
   uint32_t heavy_cap = 0;        // stack items per heavy wave
+  uint64_t blob_bytes = 0;       // topic bytes of the batch it was last sized for (k_tokenise's LDS shape)
   hipEvent_t ev = nullptr;       // recorded after its last batch
   hipStream_t stream = nullptr;  // stream of its last batch
   uint64_t used = 0;             // LRU clock

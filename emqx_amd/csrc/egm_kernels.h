@@ -82,6 +82,7 @@ struct MatchWork {                // per-batch device workspace
   uint64_t rec_cap;
   uint32_t rec_grain;             // u32 per record segment
   uint32_t flush_lim;             // staged emits that trigger a flush (<= WALK_STAGE; smaller: tests)
+  uint64_t blob_bytes;            // the batch's topic bytes, or a bound on them (picks k_tokenise's LDS shape)
   uint4* chunks;                  // [n / CHUNK + 1] ChunkRec per chunk
   uint32_t* dir;                  // [(n / CHUNK + 1) * REC_DIR] each chunk's first REC_DIR record offsets / 4
   uint32_t* ids_tmp;              // [ids_cap] ids of heavy topics (one piece each)
@@ -297,8 +298,8 @@ struct RetainWork {            // per query batch
   int ge_plain;                // dispatch: plain topics use read_message's Et >= Now
 };
 
-hipError_t launch_tokenise(const DevTable& tab, const uint8_t* blob, const uint32_t* off, uint32_t n, uint32_t* wid,
-                           uint32_t* lv, uint8_t* tfl, hipStream_t s);
+hipError_t launch_tokenise(const DevTable& tab, const uint8_t* blob, uint64_t nbytes, const uint32_t* off, uint32_t n,
+                           uint32_t* wid, uint32_t* lv, uint8_t* tfl, hipStream_t s);
 hipError_t launch_rs_alive(const RetainView& v, const RetainWork& w, hipStream_t s);
 hipError_t launch_rs_init(uint32_t n, uint32_t* pf, uint32_t* pn, hipStream_t s);
 hipError_t launch_rs_level(const RetainView& v, const RetainWork& w, uint32_t level, uint32_t np,

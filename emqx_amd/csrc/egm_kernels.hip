@@ -33,18 +33,36 @@ constexpr int MODE_TRIE = 0;
 constexpr int MODE_ROUTES = 1;
 
 constexpr int TOK_BLOCK = 256;
-#ifndef EGM_TOK_LDS
-#define EGM_TOK_LDS 16256   // staged topic bytes per tokenise block (A/B at C2: 24 KB -> 1.09 ms, 16 KB -> 0.92, 12 KB -> 1.12;
-                            // 16 KB - 128 B keeps 4 blocks per CU beside the walk-order key table)
-#endif
-constexpr int TOK_LDS = EGM_TOK_LDS;
-#ifndef EGM_TOK_WORDS
-#define EGM_TOK_WORDS 2528   // words per tokenise block (5 B of LDS each): 32 000 B per block, 25 of LDS's 1 280-B
-                             // allocation granules, so 5 blocks fit per CU (2 560 words took 26 granules: 4 blocks,
-                             // as with round 5's 7 B per word) — C2 0.882 -> 0.773 ms, C3 2.57 -> 2.27 (r6av);
-                             // 2048 made C3's segments of 128 depth-16 topics retry as two of 64
-#endif
-constexpr int TOK_WORDS = EGM_TOK_WORDS;
+// k_tokenise stages a block's topic bytes and its words' (start, length, topic) in LDS.  The two capacities are
+// run-time arguments, picked per batch from its mean topic length (tok_shape below): the block's LDS, static
+// (3 088 B: tg, tex, tflag, wsum) + dynamic (bytes + 4 + 5 B per word), is allocated in 1 280-B granules of the
+// CU's 163 840 B, so a batch of short topics gets more resident blocks than one sized for C3's.
+//
+//   shape  bytes   words  dynamic   block    granules  blocks/CU (LDS)  x 1 280 x granules
+//   0      12 288  2 296  23 772 B  26 860 B  21        6                161 280 <= 163 840
+//   1      16 256  2 528  28 900 B  31 988 B  25        5                160 000 <= 163 840
+//
+// Shape 1 is the fixed size of rounds 5-6 (A/B at C2: 24 KB of bytes -> 1.09 ms, 16 KB -> 0.92, 12 KB -> 1.12 with
+// the words static; 2 560 words took 26 granules, 4 blocks: C2 0.882 -> 0.773 ms, C3 2.57 -> 2.27 at 5 (r6av);
+// 2 048 words made C3's segments of 128 depth-16 topics retry as two of 64).  Any topic mix is tokenised correctly
+// under either: a block's segment is halved until it fits, and a single topic that does not takes a lane path.
+struct TokShape {
+  uint32_t bytes;       // staged topic bytes (a multiple of 4, < 65 536: a word's start is 16 bits of wpos)
+  uint32_t words;       // words (5 B of LDS each)
+  uint32_t mean_max;    // picked for batches of at most this many bytes per topic
+};
+constexpr TokShape TOK_SHAPES[] = {
+    {12288, 2296, 40},          // 256 topics of <= 40 B stage <= 10 243 B: C1, C2 and C4 (33-36 B, <= 9 704 B and
+                                // <= 1 743 words in any block) never halve
+    {16256, 2528, 0xFFFFFFFFu},
+};
+constexpr int TOK_N_SHAPES = sizeof(TOK_SHAPES) / sizeof(TOK_SHAPES[0]);
+constexpr uint32_t TOK_STATIC_LDS = 3 * 256 * 4 + 256 / 64 * 4;
+constexpr uint32_t tok_dyn_lds(const TokShape& sh) { return sh.bytes + 4 + sh.words * 5; }   // +4: lds_word reads one word past
+constexpr uint32_t tok_granules(const TokShape& sh) { return (TOK_STATIC_LDS + tok_dyn_lds(sh) + 1279) / 1280; }
+static_assert(tok_granules(TOK_SHAPES[0]) * 6 * 1280 <= 163840, "shape 0: 6 blocks per CU");
+static_assert(tok_granules(TOK_SHAPES[1]) * 5 * 1280 <= 163840, "shape 1: 5 blocks per CU");
+static_assert(TOK_SHAPES[0].bytes % 4 == 0 && TOK_SHAPES[1].bytes % 4 == 0 && TOK_SHAPES[1].bytes < 65536, "wpos layout");
 #ifndef EGM_TOK_U
 #define EGM_TOK_U 2          // words per lane whose dictionary probes are in flight together
 #endif
@@ -242,17 +260,27 @@ __device__ __forceinline__ uint64_t sort_val(uint32_t t, uint32_t D, uint32_t f,
 //   2. lane per topic: record every word's (start, length, output index)
 //   3. lane per word, two words per lane in flight: FNV-1a of its bytes, the
 //      '+'/'#' words, the byte-exact dictionary probe -> wid[off[t] + t + l]
+// Pass 1 keeps what it found: a topic's '/' positions as a 128-bit map over
+// the bytes from its first staged word on, which pass 2 walks bit by bit
+// instead of reading the bytes again (a topic that overruns the map, > 125 B
+// or so, is rescanned — a choice per lane).
 // The block's topics are taken in segments of S topics, S halved until the
-// segment's bytes fit TOK_LDS and its words TOK_WORDS (C3's depth-16 topics
-// of ~100 B: two segments of 128).  Only a single topic too long for LDS
-// takes the lane-per-topic path from global memory.
-__global__ __launch_bounds__(TOK_BLOCK) void k_tokenise(DevTable tab, const uint8_t* __restrict__ blob,
+// segment's bytes fit cap_bytes and its words cap_words (TOK_SHAPES; C3's
+// depth-16 topics of ~100 B: two segments of 128).  Only a single topic too
+// long for LDS takes the lane-per-topic path from global memory.
+// 6 blocks per CU are 6 waves per SIMD: 80 VGPRs, which the kernel compiles to
+// without a spill (82 unbounded; 7 blocks would need 72 and spills 10, so no
+// shape asks for 7).
+extern __shared__ __attribute__((aligned(16))) uint32_t tok_lds[];   // tok_dyn_lds(shape) bytes
+
+__global__ __launch_bounds__(TOK_BLOCK, 6) void k_tokenise(DevTable tab, const uint8_t* __restrict__ blob,
                                                         const uint32_t* __restrict__ off, uint32_t n,
                                                         uint32_t* __restrict__ wid, uint32_t* __restrict__ lv,
-                                                        uint8_t* __restrict__ tfl, WalkOrderOut wo) {
-  __shared__ __attribute__((aligned(16))) uint32_t sw[TOK_LDS / 4 + 1];   // +1: lds_word reads one word past
-  __shared__ uint32_t wpos[TOK_WORDS];   // start | len << 16 (LDS byte index); then the word's id (sorted batch)
-  __shared__ uint8_t wtop[TOK_WORDS];    // topic within the segment
+                                                        uint8_t* __restrict__ tfl, WalkOrderOut wo,
+                                                        uint32_t cap_bytes, uint32_t cap_words) {
+  uint32_t* const sw = tok_lds;                        // cap_bytes / 4 + 1 words (lds_word reads one word past)
+  uint32_t* const wpos = sw + (cap_bytes >> 2) + 1;    // start | len << 16 (LDS byte index); then the word's id (sorted batch)
+  uint8_t* const wtop = (uint8_t*)(wpos + cap_words);  // topic within the segment
   __shared__ uint32_t tg[TOK_BLOCK];     // wid index of the topic's word 0 (a word's is tg + its level)
   __shared__ uint32_t tex[TOK_BLOCK];    // the topic's first word in the segment (a word's level is i - tex)
   __shared__ uint32_t tflag[TOK_BLOCK];   // TF_* flags | levels << 8
@@ -271,11 +299,11 @@ __global__ __launch_bounds__(TOK_BLOCK) void k_tokenise(DevTable tab, const uint
       t1 = min(t0 + S, tend);
       sa = off[t0] & ~3u;
       ea = (off[t1] + 3u) & ~3u;   // blob is readable up to a multiple of 4 (ABI)
-      if ((ea - sa) <= (uint32_t)TOK_LDS || S == 1) break;
+      if ((ea - sa) <= cap_bytes || S == 1) break;
       S >>= 1;
     }
     const uint32_t t = t0 + tid;
-    if ((ea - sa) > (uint32_t)TOK_LDS) {   // one topic longer than LDS: lane path from global memory
+    if ((ea - sa) > cap_bytes) {   // one topic longer than LDS: lane path from global memory
       if (tid == 0) {
         const uint32_t ts = off[t0], len = off[t0 + 1] - ts;
         uint32_t l;
@@ -301,13 +329,18 @@ __global__ __launch_bounds__(TOK_BLOCK) void k_tokenise(DevTable tab, const uint
 
     // ---- pass 1: levels per topic ----
     uint32_t ts = 0, len = 0, D = 0, fl = 0;
+    uint64_t sl0 = 0, sl1 = 0;   // bit i: byte (ts & ~3) + i (+ 64 for sl1) is a '/' of this topic
     if (t < t1) {
       ts = off[t] - sa;
       len = off[t + 1] - off[t];
-      uint32_t c = 0;
-      for (uint32_t q = ts & ~3u; q < ts + len; q += 4) {
+      uint32_t c = 0, j = 0;
+      for (uint32_t q = ts & ~3u; q < ts + len; q += 4, j += 4) {
         const uint32_t lo = q < ts ? ts - q : 0u, hi = min(4u, ts + len - q);
-        c += popc((uint64_t)(slash_mask(sw[q >> 2]) & byte_range(lo, hi)));
+        const uint32_t m = slash_mask(sw[q >> 2]) & byte_range(lo, hi);
+        c += popc((uint64_t)m);
+        const uint64_t nib = (((m >> 7) * 0x00204081u) >> 21) & 0xFu;   // bit 7 of byte k -> bit k
+        if (j < 64) sl0 |= nib << j;
+        else if (j < 128) sl1 |= nib << (j - 64);
       }
       D = c + 1;
       if (len > 0 && lds_byte(sw, ts) == '$') fl |= TF_DOLLAR;
@@ -324,7 +357,7 @@ __global__ __launch_bounds__(TOK_BLOCK) void k_tokenise(DevTable tab, const uint
       W += wsum[k];
     }
     __syncthreads();   // wsum and sw are rewritten by the next segment
-    if (W > (uint32_t)TOK_WORDS) {
+    if (W > cap_words) {
       if (S > 1) {     // too many words: retry the same topics in a smaller segment
         S >>= 1;
         continue;
@@ -351,16 +384,23 @@ __global__ __launch_bounds__(TOK_BLOCK) void k_tokenise(DevTable tab, const uint
     if (t < t1) {
       const uint32_t g = off[t] + t;   // wid index of the topic's first word
       uint32_t l = 0, ws = ts;
-      for (uint32_t q = ts & ~3u; q < ts + len; q += 4) {
-        const uint32_t lo = q < ts ? ts - q : 0u, hi = min(4u, ts + len - q);
-        uint32_t m = slash_mask(sw[q >> 2]) & byte_range(lo, hi);
-        while (m) {
-          const uint32_t p = q + (__builtin_ctz(m) >> 3);
-          m &= m - 1;
-          wpos[ex + l] = ws | ((p - ws) << 16);
-          wtop[ex + l] = (uint8_t)tid;
-          ++l;
-          ws = p + 1;
+      auto word_ends = [&](uint32_t p) {   // a '/' at LDS byte p
+        wpos[ex + l] = ws | ((p - ws) << 16);
+        wtop[ex + l] = (uint8_t)tid;
+        ++l;
+        ws = p + 1;
+      };
+      if ((ts & 3u) + len <= 128) {   // every '/' is in pass 1's map
+        for (; sl0; sl0 &= sl0 - 1) word_ends((ts & ~3u) + (uint32_t)__builtin_ctzll(sl0));
+        for (; sl1; sl1 &= sl1 - 1) word_ends((ts & ~3u) + 64 + (uint32_t)__builtin_ctzll(sl1));
+      } else {
+        for (uint32_t q = ts & ~3u; q < ts + len; q += 4) {
+          const uint32_t lo = q < ts ? ts - q : 0u, hi = min(4u, ts + len - q);
+          uint32_t m = slash_mask(sw[q >> 2]) & byte_range(lo, hi);
+          while (m) {
+            word_ends(q + (__builtin_ctz(m) >> 3));
+            m &= m - 1;
+          }
         }
       }
       wpos[ex + l] = ws | ((ts + len - ws) << 16);
@@ -2028,6 +2068,23 @@ hipError_t launch_walk_sort(uint32_t* keys, uint32_t* keys_tmp, uint64_t* vals, 
 
 constexpr uint32_t SORT_MIN_TOPICS = 16384;   // below this the sort's fixed cost outweighs the locality
 
+// k_tokenise's LDS shape for a batch of n topics in nbytes: the first of TOK_SHAPES that takes its mean topic length.
+// EGM_TOK_SHAPE=<index> pins one (tests, A/B; read at every batch, like EGM_WALK_KEY).
+static const TokShape& tok_shape(uint64_t nbytes, uint32_t n) {
+  const char* v = getenv("EGM_TOK_SHAPE");
+  if (v && *v >= '0' && *v < '0' + TOK_N_SHAPES && !v[1]) return TOK_SHAPES[*v - '0'];
+  int k = 0;
+  while (k + 1 < TOK_N_SHAPES && nbytes > (uint64_t)TOK_SHAPES[k].mean_max * n) ++k;
+  return TOK_SHAPES[k];
+}
+
+static void launch_k_tokenise(const DevTable& tab, const uint8_t* blob, uint64_t nbytes, const uint32_t* off, uint32_t n,
+                              uint32_t* wid, uint32_t* lv, uint8_t* tfl, const WalkOrderOut& wo, hipStream_t s) {
+  const TokShape& sh = tok_shape(nbytes, n);
+  hipLaunchKernelGGL(k_tokenise, dim3((n + TOK_BLOCK - 1) / TOK_BLOCK), dim3(TOK_BLOCK), tok_dyn_lds(sh), s, tab, blob,
+                     off, n, wid, lv, tfl, wo, sh.bytes, sh.words);
+}
+
 hipError_t launch_match(const DevTable& tab, const uint8_t* blob, const uint32_t* off, uint32_t n,
                         int mode, const MatchWork& w_in, const MatchOut& out, hipStream_t s,
                         hipEvent_t* ev_walk, bool* walk_sorted) {
@@ -2051,8 +2108,7 @@ hipError_t launch_match(const DevTable& tab, const uint8_t* blob, const uint32_t
   WalkOrderOut wo{};
   if (sorted) wo = WalkOrderOut{w.skey, w.sval, w.wfix, w.key_shape, nullptr};
   wo.n_live = w.n_live;
-  hipLaunchKernelGGL(k_tokenise, dim3((n + TOK_BLOCK - 1) / TOK_BLOCK), dim3(TOK_BLOCK), 0, s, tab, blob,
-                     off, n, w.wid, w.lv, w.tfl, wo);
+  launch_k_tokenise(tab, blob, w.blob_bytes, off, n, w.wid, w.lv, w.tfl, wo, s);
   trace(s, "k_tokenise");
   if (sorted) {
     e = walk_sort(w, n, kbits, s);
@@ -2897,12 +2953,11 @@ __global__ __launch_bounds__(256) void k_rs_expand(RetainView v, RetainWork w, u
   }
 }
 
-hipError_t launch_tokenise(const DevTable& tab, const uint8_t* blob, const uint32_t* off, uint32_t n, uint32_t* wid,
-                           uint32_t* lv, uint8_t* tfl, hipStream_t s) {
+hipError_t launch_tokenise(const DevTable& tab, const uint8_t* blob, uint64_t nbytes, const uint32_t* off, uint32_t n,
+                           uint32_t* wid, uint32_t* lv, uint8_t* tfl, hipStream_t s) {
   const WalkOrderOut none{};
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(k_tokenise, dim3((n + TOK_BLOCK - 1) / TOK_BLOCK), dim3(TOK_BLOCK), 0, s, tab, blob, off, n,
-                     wid, lv, tfl, none);
+  launch_k_tokenise(tab, blob, nbytes, off, n, wid, lv, tfl, none, s);
   return hipGetLastError();
 }
 

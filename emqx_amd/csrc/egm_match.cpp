@@ -69,6 +69,7 @@ int egm::ensure_work(egm_ctx* c, MatchWs& W, uint32_t n, uint64_t blob_bytes, ui
                      uint64_t max_levels) {
   hipError_t e;
   const uint64_t nn = (uint64_t)n + 1;
+  W.blob_bytes = blob_bytes;
   if ((e = W.wid.ensure((blob_bytes + nn) * 4)) != hipSuccess) return c->hip_fail(e, "wid");
   if ((e = W.lv.ensure(nn * 4)) != hipSuccess) return c->hip_fail(e, "lv");
   if ((e = W.tfl.ensure(nn)) != hipSuccess) return c->hip_fail(e, "tfl");
@@ -122,6 +123,7 @@ static MatchWork work_view(egm_ctx* c, MatchWs& W) {
   w.rec_cap = W.rec_cap;
   w.rec_grain = W.rec_grain;
   w.flush_lim = W.flush_lim;
+  w.blob_bytes = W.blob_bytes;
   w.chunks = W.chunks.as<uint4>();
   w.dir = W.dir.as<uint32_t>();
   w.ids_tmp = W.ids_tmp.as<uint32_t>();

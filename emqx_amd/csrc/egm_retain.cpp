@@ -383,7 +383,7 @@ int egm_rstore_match(egm_rstore* r, const uint8_t* blob, const uint32_t* off, ui
   if ((e = r->tiles.ensure(tiles_need))) return r->hip_fail(e, "tiles");
   w.tiles = r->tiles.as<uint64_t>();
 
-  if ((e = launch_tokenise(r->dtab, r->in_blob.as<uint8_t>(), w.off, n, r->wid.as<uint32_t>(), r->lv.as<uint32_t>(),
+  if ((e = launch_tokenise(r->dtab, r->in_blob.as<uint8_t>(), bytes, w.off, n, r->wid.as<uint32_t>(), r->lv.as<uint32_t>(),
                            r->tfl.as<uint8_t>(), s)) ||
       (e = launch_rs_alive(r->view, w, s)))
     return r->hip_fail(e, "tokenise/alive");
