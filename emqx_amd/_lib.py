@@ -140,6 +140,10 @@ SIGNATURES = {
     "egm_rstore_clean": (C.c_int, [_P]),
     "egm_rstore_size": (C.c_int, [_P, _u64p]),
     "egm_rstore_commit": (C.c_int, [_P]),
+    "egm_rstore_rebuild": (C.c_int, [_P]),
+    "egm_rstore_set_overlay_cap": (C.c_int, [_P, C.c_uint32]),
+    "egm_rstore_last_commit": (C.c_int, [_P, C.POINTER(C.c_int), _u64p, _u64p, _u64p, _u64p, _u64p]),
+    "egm_rstore_clear_expired": (C.c_int, [_P, C.c_uint64, C.POINTER(_u32p), _u64p]),
     "egm_rstore_match": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint64, C.c_int,
                                    C.POINTER(C.POINTER(egm_result))]),
     "egm_image_new": (_P, []),

@@ -260,22 +260,34 @@ hipError_t launch_prefix_route(const uint8_t* blob, const uint32_t* off, uint32_
                                uint32_t n_vparts, const PrefixSlots& ps, uint8_t* send, unsigned long long* ctr,
                                uint64_t* dst, hipStream_t s);
 
-// Scatter n records of rec_bytes (4, 16 or 32) from src[] to dst[idx[i]]:
-// the incremental epoch commit of egm_capi.cpp.
+// Scatter n records of rec_bytes (4, 8, 16 or 32) from src[] to dst[idx[i]]:
+// the incremental commits of egm_capi.cpp, egm_fanout.cpp and egm_retain.cpp.
 hipError_t launch_patch(void* dst, uint32_t rec_bytes, const uint32_t* idx, const void* src, uint64_t n,
                         hipStream_t s);
 
 // ---- retained reverse match (emqx_retainer_mnesia:match_messages/1) ----
 constexpr uint32_t RN_TERM = 0x80000000u;   // node's own topic is stored (in n_children)
 constexpr uint32_t RS_SINGLE = 0x80000000u; // range = one already-checked rank (in hi)
+constexpr uint32_t RS_TOMB = 0xFFFFFFFFu;   // msg[rank]: the topic was deleted since the image was built
 
 struct RetainView {            // a committed retained store in HBM
   const uint4* nodes;          // {first_child, n_children | RN_TERM, lo, hi}: ranks under the node
   const uint4* edges;          // 16 B {parent, word, child, 0}, 4 per 64 B bucket
   uint32_t edge_mask;          // buckets - 1
-  const uint32_t* msg;         // rank -> message id
+  const uint32_t* msg;         // rank -> message id (RS_TOMB: deleted, dead for every `now`)
   const uint64_t* expiry;      // rank -> expiry time in ms (0 = never)
   uint32_t n_topics;
+};
+
+struct RetainOverlay {         // topics stored since the image was built, matched on their bytes
+  const uint8_t* blob;         // topic bytes
+  const uint32_t* off;         // [n + 1] into blob
+  const uint32_t* levels;      // words per topic
+  const uint32_t* msg;
+  const uint64_t* expiry;
+  uint32_t n;
+  uint64_t* mask;              // per (filter, tile of 64 topics): the matching lanes
+  uint32_t* base;              // ... and where they start inside the filter's row
 };
 
 struct RetainWork {            // per query batch
@@ -306,8 +318,15 @@ hipError_t launch_rs_level(const RetainView& v, const RetainWork& w, uint32_t le
                            const uint32_t* pf, const uint32_t* pn, hipStream_t s);
 hipError_t launch_rs_fill(const RetainWork& w, uint32_t np, uint64_t nnext, const uint32_t* pf, uint32_t* pf2,
                           uint32_t* pn2, hipStream_t s);
-hipError_t launch_rs_rows(const RetainWork& w, uint32_t nr, uint32_t n, uint64_t* row, hipStream_t s);
+// counts per filter (image ranges, then the overlay's byte match against the
+// filters in fblob/w.off) and their scan into row[n + 1]
+hipError_t launch_rs_rows(const RetainWork& w, const RetainOverlay& o, const uint8_t* fblob, uint32_t nr, uint32_t n,
+                          uint64_t* row, hipStream_t s);
 hipError_t launch_rs_expand(const RetainView& v, const RetainWork& w, uint32_t nr, const uint64_t* row,
                             uint32_t* ids, hipStream_t s);
+hipError_t launch_rs_ov_fill(const RetainOverlay& o, uint32_t n, const uint64_t* row, uint32_t* ids, hipStream_t s);
+// clear_expired/1: tombstones the image ranks with 0 < expiry < now, appends them to out[m], *n_out = how many
+hipError_t launch_rs_expire(const uint64_t* expiry, uint32_t* msg, uint32_t m, uint64_t now, uint32_t* out,
+                            uint32_t* n_out, hipStream_t s);
 
 }  // namespace egm

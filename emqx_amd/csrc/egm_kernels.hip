@@ -2742,14 +2742,23 @@ __global__ __launch_bounds__(256) void k_patch_u32(uint32_t* __restrict__ dst, c
     dst[idx[i]] = src[i];
 }
 
+__global__ __launch_bounds__(256) void k_patch_u64(uint64_t* __restrict__ dst, const uint32_t* __restrict__ idx,
+                                                   const uint64_t* __restrict__ src, uint64_t n) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+    dst[idx[i]] = src[i];
+}
+
 hipError_t launch_patch(void* dst, uint32_t rec_bytes, const uint32_t* idx, const void* src, uint64_t n,
                         hipStream_t s) {
   if (!n) return hipSuccess;
-  const uint64_t lanes = rec_bytes == 4 ? n : n * (rec_bytes / 16);
+  const uint64_t lanes = rec_bytes < 16 ? n : n * (rec_bytes / 16);
   const uint32_t g = (uint32_t)std::min<uint64_t>((lanes + 255) / 256, 4096);
   switch (rec_bytes) {
     case 4:
       hipLaunchKernelGGL(k_patch_u32, dim3(g), dim3(256), 0, s, (uint32_t*)dst, idx, (const uint32_t*)src, n);
+      break;
+    case 8:
+      hipLaunchKernelGGL(k_patch_u64, dim3(g), dim3(256), 0, s, (uint64_t*)dst, idx, (const uint64_t*)src, n);
       break;
     case 16:
       hipLaunchKernelGGL(k_patch<1>, dim3(g), dim3(256), 0, s, (uint4*)dst, idx, (const uint4*)src, n);
@@ -2808,10 +2817,13 @@ __device__ __forceinline__ void rs_emit(const RetainWork& w, bool on, uint32_t f
   }
 }
 
-__global__ __launch_bounds__(256) void k_rs_alive(const uint64_t* __restrict__ expiry, uint32_t m, uint64_t now,
+// a tombstoned rank (msg == RS_TOMB: its topic was deleted after the image was
+// built) is dead for every `now`
+__global__ __launch_bounds__(256) void k_rs_alive(const uint64_t* __restrict__ expiry,
+                                                  const uint32_t* __restrict__ msg, uint32_t m, uint64_t now,
                                                   uint32_t* __restrict__ alive) {
   for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < m; r += gridDim.x * blockDim.x)
-    alive[r] = rs_alive(expiry[r], now, false) ? 1u : 0u;
+    alive[r] = (msg[r] != RS_TOMB && rs_alive(expiry[r], now, false)) ? 1u : 0u;
 }
 
 __global__ __launch_bounds__(256) void k_rs_init(uint32_t n, uint32_t* __restrict__ pf, uint32_t* __restrict__ pn) {
@@ -2838,7 +2850,7 @@ __global__ __launch_bounds__(256) void k_rs_step(RetainView v, RetainWork w, uin
       uint32_t c = 0, aux = 0;
       if (level == L) {                  // every word consumed: the topic at this node
         const bool ge = w.ge_plain && !(w.tfl[f] & TF_WILDCARD);
-        if ((rec.y & RN_TERM) && rs_alive(v.expiry[rec.z], w.now, ge)) {
+        if ((rec.y & RN_TERM) && v.msg[rec.z] != RS_TOMB && rs_alive(v.expiry[rec.z], w.now, ge)) {
           emit = true;
           lo = rec.z;
           hi = (rec.z + 1) | RS_SINGLE;
@@ -2953,6 +2965,142 @@ __global__ __launch_bounds__(256) void k_rs_expand(RetainView v, RetainWork w, u
   }
 }
 
+// ---- overlay: topics stored since the image was built --------------------
+// They may hold words the image's dictionary has never seen, and only a
+// rebuild numbers words, so the overlay is matched on bytes: one wave per
+// (filter, tile of 64 overlay topics), one lane per topic; the filter's bytes
+// are the same for the whole wave.  condition/1 (:215-220) word by word: '+'
+// takes exactly one word (an empty one too), a LAST '#' any rest (also none),
+// a '#' elsewhere matches nothing; no '$' rule; bytes compared exactly.
+// Every loop is bounded by the filter's or the topic's byte length.
+//
+// k_rs_ov_count stores the wave's ballot per (filter, tile), adds its popcount
+// to fcnt[f] with one atomic (the counter k_rs_count's ranges reserve from) and
+// keeps the returned base; k_rs_ov_fill writes the ids from the stored mask
+// once the rows are scanned, without a second compare.
+__global__ __launch_bounds__(256) void k_rs_ov_count(RetainOverlay o, RetainWork w, const uint8_t* __restrict__ fblob,
+                                                     uint32_t n) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t tiles = (o.n + 63) >> 6;
+  const uint64_t n_pairs = (uint64_t)n * tiles;
+  const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  for (uint64_t q = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); q < n_pairs; q += nw) {
+    const uint32_t f = (uint32_t)(q / tiles), tile = (uint32_t)(q % tiles);
+    const uint8_t* fp = fblob + w.off[f];
+    const uint32_t flen = w.off[f + 1] - w.off[f];
+    // the filter's word count, the wave counting '/' together (uniform trips)
+    uint32_t L = 1;
+    for (uint32_t b0 = 0; b0 < flen; b0 += 64) {
+      const uint32_t b = b0 + lane;
+      L += (uint32_t)__popcll(__ballot(b < flen && fp[b] == '/'));
+    }
+    const bool last_hash = flen >= 1 && fp[flen - 1] == '#' && (flen == 1 || fp[flen - 2] == '/');
+    const uint32_t p = tile * 64 + lane;
+    bool ok = false;
+    uint32_t tb = 0, tlen = 0;
+    if (p < o.n) {
+      const uint32_t lv = o.levels[p];
+      ok = last_hash ? lv + 1 >= L : lv == L;   // level-count prefilter
+      tb = o.off[p];
+      tlen = o.off[p + 1] - tb;
+    }
+    const uint8_t* tp = o.blob + tb;
+    bool wild = false;
+    if (__ballot(ok)) {
+      uint32_t i = 0;        // filter position: the same in every lane
+      uint32_t j = 0;        // topic position
+      bool tdone = false;    // the topic has no word left
+      for (;;) {
+        uint32_t ie = i;
+        while (ie < flen && fp[ie] != '/') ++ie;
+        const uint32_t wl = ie - i;
+        const bool last = ie == flen;
+        const uint8_t c0 = wl == 1 ? fp[i] : (uint8_t)0;
+        if (c0 == '#') {
+          wild = true;
+          if (!last) ok = false;
+          break;               // last: whatever is left of the topic, also nothing
+        }
+        if (ok) {
+          if (tdone) {
+            ok = false;
+          } else {
+            uint32_t je;
+            if (c0 == '+') {
+              je = j;
+              while (je < tlen && tp[je] != '/') ++je;
+            } else {
+              uint32_t k = 0;
+              while (k < wl && j + k < tlen && tp[j + k] == fp[i + k]) ++k;
+              je = j + wl;
+              if (k < wl || (je < tlen && tp[je] != '/')) ok = false;
+            }
+            if (ok) {
+              if (je == tlen) tdone = true;
+              else j = je + 1;
+            }
+          }
+        }
+        if (c0 == '+') wild = true;
+        if (last) {
+          ok = ok && tdone;
+          break;
+        }
+        i = ie + 1;
+      }
+      if (ok) ok = rs_alive(o.expiry[p], w.now, w.ge_plain && !wild);
+    }
+    const uint64_t m = __ballot(ok);
+    if (lane == 0) {
+      o.mask[q] = m;
+      o.base[q] = m ? atomicAdd(&w.fcnt[f], (uint32_t)__popcll(m)) : 0u;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_rs_ov_fill(RetainOverlay o, uint32_t n, const uint64_t* __restrict__ row,
+                                                    uint32_t* __restrict__ ids) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t tiles = (o.n + 63) >> 6;
+  const uint64_t n_pairs = (uint64_t)n * tiles;
+  const uint64_t nw = (uint64_t)gridDim.x * (blockDim.x >> 6);
+  for (uint64_t q = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); q < n_pairs; q += nw) {
+    const uint64_t m = o.mask[q];
+    if (!((m >> lane) & 1)) continue;
+    const uint32_t f = (uint32_t)(q / tiles), tile = (uint32_t)(q % tiles);
+    ids[row[f] + o.base[q] + (uint32_t)__popcll(m & ((1ull << lane) - 1))] = o.msg[tile * 64 + lane];
+  }
+}
+
+// clear_expired/1 (emqx_retainer_mnesia.erl:103-112) over the image: a rank
+// with 0 < expiry < now that is not a tombstone yet becomes one, and its rank
+// is appended to `out` (wave-aggregated, as rs_emit).  out holds m ranks.
+__global__ __launch_bounds__(256) void k_rs_expire(const uint64_t* __restrict__ expiry, uint32_t* __restrict__ msg,
+                                                   uint32_t m, uint64_t now, uint32_t* __restrict__ out,
+                                                   uint32_t* __restrict__ n_out) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t stride = gridDim.x * blockDim.x;
+  const uint32_t n_iter = (m + stride - 1) / stride;   // uniform trip count: the wave ballots
+  for (uint32_t it = 0; it < n_iter; ++it) {
+    const uint64_t r = (uint64_t)it * stride + blockIdx.x * blockDim.x + threadIdx.x;
+    bool on = false;
+    if (r < m) {
+      const uint64_t e = expiry[r];
+      on = e != 0 && e < now && msg[r] != RS_TOMB;
+    }
+    const uint64_t b = __ballot(on);
+    if (!b) continue;
+    const uint32_t leader = __builtin_ctzll(b);
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(n_out, (uint32_t)__popcll(b));
+    base = __shfl(base, leader, 64);
+    if (on) {
+      msg[r] = RS_TOMB;
+      out[base + (uint32_t)__popcll(b & ((1ull << lane) - 1))] = (uint32_t)r;   // < m: each rank is appended once
+    }
+  }
+}
+
 hipError_t launch_tokenise(const DevTable& tab, const uint8_t* blob, uint64_t nbytes, const uint32_t* off, uint32_t n,
                            uint32_t* wid, uint32_t* lv, uint8_t* tfl, hipStream_t s) {
   const WalkOrderOut none{};
@@ -2967,7 +3115,8 @@ static uint32_t grid_for(uint64_t n, uint32_t cap = 8192) {
 
 hipError_t launch_rs_alive(const RetainView& v, const RetainWork& w, hipStream_t s) {
   if (v.n_topics) {
-    hipLaunchKernelGGL(k_rs_alive, dim3(grid_for(v.n_topics)), dim3(256), 0, s, v.expiry, v.n_topics, w.now, w.alive);
+    hipLaunchKernelGGL(k_rs_alive, dim3(grid_for(v.n_topics)), dim3(256), 0, s, v.expiry, v.msg, v.n_topics, w.now,
+                       w.alive);
   }
   scan_counts(w.alive, v.n_topics, w.tiles, w.apre, s);
   return hipGetLastError();
@@ -2991,11 +3140,32 @@ hipError_t launch_rs_fill(const RetainWork& w, uint32_t np, uint64_t nnext, cons
   return hipGetLastError();
 }
 
-hipError_t launch_rs_rows(const RetainWork& w, uint32_t nr, uint32_t n, uint64_t* row, hipStream_t s) {
+// one wave per (filter, overlay tile): blocks of 4 waves
+static uint32_t ov_grid(const RetainOverlay& o, uint32_t n) {
+  const uint64_t pairs = (uint64_t)n * ((o.n + 63) >> 6);
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((pairs + 3) / 4, 16384));
+}
+
+hipError_t launch_rs_rows(const RetainWork& w, const RetainOverlay& o, const uint8_t* fblob, uint32_t nr, uint32_t n,
+                          uint64_t* row, hipStream_t s) {
   hipError_t e = hipMemsetAsync(w.fcnt, 0, ((size_t)n + 1) * 4, s);
   if (e != hipSuccess) return e;
   if (nr) hipLaunchKernelGGL(k_rs_count, dim3(grid_for(nr)), dim3(256), 0, s, w, nr);
+  if (o.n && n) hipLaunchKernelGGL(k_rs_ov_count, dim3(ov_grid(o, n)), dim3(256), 0, s, o, w, fblob, n);
   scan_counts(w.fcnt, n, w.tiles, row, s);
+  return hipGetLastError();
+}
+
+hipError_t launch_rs_ov_fill(const RetainOverlay& o, uint32_t n, const uint64_t* row, uint32_t* ids, hipStream_t s) {
+  if (o.n && n) hipLaunchKernelGGL(k_rs_ov_fill, dim3(ov_grid(o, n)), dim3(256), 0, s, o, n, row, ids);
+  return hipGetLastError();
+}
+
+hipError_t launch_rs_expire(const uint64_t* expiry, uint32_t* msg, uint32_t m, uint64_t now, uint32_t* out,
+                            uint32_t* n_out, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(n_out, 0, 4, s);
+  if (e != hipSuccess) return e;
+  if (m) hipLaunchKernelGGL(k_rs_expire, dim3(grid_for(m)), dim3(256), 0, s, expiry, msg, m, now, out, n_out);
   return hipGetLastError();
 }
 

@@ -6,6 +6,7 @@
 //   delete_message/2 :114-129 -> egm_rstore_delete  (plain topic; a wildcard
 //                                delete is match + delete, see retainer.py)
 //   clean/1          :148-150 -> egm_rstore_clean
+//   clear_expired/1  :103-112 -> egm_rstore_clear_expired
 //   match_messages/1 :200-204 -> egm_rstore_match   (condition/1 :215-220,
 //                                make_match_spec/1 :222-228)
 //   read_messages/1  :187-198 -> egm_rstore_match, EGM_RMODE_DISPATCH
@@ -14,7 +15,14 @@
 // numbered breadth-first (children contiguous), topics ranked depth-first so
 // the topics under a node are one rank range; a (node, word) -> child hash
 // table; the dictionary in the layout k_tokenise reads; rank -> message id and
-// expiry.  The image is rebuilt from the host records at each commit.
+// expiry.
+//
+// Commits are incremental: a put on a topic of the image patches
+// msg[rank] and expiry[rank] in place, a delete makes the rank a tombstone
+// (msg[rank] = RS_TOMB), and a topic the image does not hold goes into the
+// overlay, a small device list that the match compares byte by byte
+// (RetainOverlay).  The image is rebuilt from the records only when
+// rs_commit_locked says so.
 #include <hip/hip_runtime_api.h>
 #include <stdlib.h>
 #include <string.h>
@@ -42,12 +50,23 @@ hipError_t put_vec(DevBuf& b, const std::vector<T>& v) {
   return e;
 }
 
+// One record per topic.  A topic is in the image (rank != NONE) or in the
+// overlay (ov != NONE), never both.  A deleted image topic stays in the map,
+// marked dead, until the next rebuild: its rank is a tombstone on the device
+// and a later put of the topic revives that rank.
 struct Rec {
-  uint32_t msg;
-  uint64_t expiry;
+  uint32_t msg = 0;
+  uint64_t expiry = 0;
+  uint32_t rank = NONE;    // image rank
+  uint32_t ov = NONE;      // index in egm_rstore::ov_ents
+  bool dead = false;       // image topic, deleted
+  bool dev_dead = false;   // the device holds a tombstone at the rank
+  bool dirty = false;      // the rank is queued in egm_rstore::touched
 };
+using RecMap = std::unordered_map<std::string, Rec>;
+using Ent = RecMap::value_type;   // node-based map: an entry's address is stable until it is erased
 
-// The host image (built at commit).
+// The host image (built at a rebuild).
 struct Image {
   std::vector<uint4> nodes;           // RetainView::nodes
   std::vector<uint4> edges;           // 16 B slots, 4 per bucket
@@ -70,12 +89,13 @@ bool split_words(const std::string& t, std::vector<std::pair<uint32_t, uint32_t>
   return true;
 }
 
-void build_image(const std::unordered_map<std::string, Rec>& recs, Image* im) {
+// ents: the live records; on return they carry their ranks and by_rank lists them in rank order
+void build_image(const std::vector<Ent*>& ents, Image* im, std::vector<Ent*>* by_rank) {
   // dictionary: every distinct topic word, in the k_tokenise probe layout
   std::unordered_map<std::string, uint32_t> wmap;
   std::vector<const std::string*> topics;
-  topics.reserve(recs.size());
-  for (const auto& kv : recs) topics.push_back(&kv.first);
+  topics.reserve(ents.size());
+  for (const Ent* e : ents) topics.push_back(&e->first);
   std::vector<uint64_t> woff(1, 0);   // per topic: first word in flat
   std::vector<uint32_t> flat;
   std::vector<std::pair<uint32_t, uint32_t>> ws;
@@ -132,6 +152,7 @@ void build_image(const std::unordered_map<std::string, Rec>& recs, Image* im) {
   std::vector<uint32_t> path(1, 0);            // path[d] = node after d words
   im->msg.resize(M);
   im->expiry.resize(M);
+  by_rank->resize(M);
   for (uint32_t r = 0; r < M; ++r) {
     const uint32_t t = order[r];
     const uint64_t a = woff[t], b = woff[t + 1];
@@ -146,9 +167,13 @@ void build_image(const std::unordered_map<std::string, Rec>& recs, Image* im) {
       path.push_back((uint32_t)dn.size() - 1);
     }
     dn[path[D]].term = true;   // D >= 1: words/1 of any topic has >= 1 word
-    const Rec& rec = recs.at(*topics[t]);
+    Rec& rec = ents[t]->second;
     im->msg[r] = rec.msg;
     im->expiry[r] = rec.expiry;
+    rec.rank = r;
+    rec.ov = NONE;
+    rec.dev_dead = rec.dirty = false;
+    (*by_rank)[r] = ents[t];
   }
   // breadth-first numbering: the children of a node are contiguous
   const uint32_t N = (uint32_t)dn.size();
@@ -207,17 +232,32 @@ struct egm_rstore {
   int device = 0;
   hipStream_t stream = nullptr;
   std::mutex mu;
-  std::unordered_map<std::string, Rec> recs;
-  bool dirty = true;
   std::string err;
+  // host records and what changed since the last commit
+  RecMap recs;                   // live records, and the dead topics of the image
+  uint64_t n_live = 0;
+  std::vector<Ent*> by_rank;     // image rank -> record
+  std::vector<Ent*> ov_ents;     // the overlay, in its device order
+  std::vector<uint32_t> touched; // image ranks to patch
+  uint64_t dead_ranks = 0;       // tombstones on the device
+  uint32_t ov_cap = 4096;
+  bool reset = true;             // the image is to be dropped (a new store, clean)
+  bool ov_dirty = false;         // the device overlay is out of date
+  struct {
+    int rebuilt = 0;
+    uint64_t patched = 0, tombstoned = 0, overlay = 0, dead = 0, h2d = 0;
+  } last;
   // committed image
   DevBuf nodes, edges, dict, dict_blob, dict_off, msg, expiry;
   RetainView view{};
   DevTable dtab{};
   uint64_t n_nodes = 0;
+  // overlay and patch staging
+  DevBuf ovbuf, pbuf, xout, xn;
+  RetainOverlay ov{};
   // per-batch workspace
   DevBuf in_blob, in_off, wid, lv, tfl, pf[2], pn[2], pc, paux, poff, tiles, rf, rlo, rhi, nr, alive, apre, fcnt, roff,
-      row, ids;
+      row, ids, ovmask, ovbase;
 
   int fail(int code, const std::string& m) {
     err = m;
@@ -227,19 +267,32 @@ struct egm_rstore {
     err = std::string(where) + ": " + hipGetErrorString(e);
     return EGM_E_DEVICE;
   }
+  void touch(Rec& x) {
+    if (!x.dirty) touched.push_back(x.rank);
+    x.dirty = true;
+  }
+  void ov_remove(Rec& x) {
+    Ent* last = ov_ents.back();
+    ov_ents[x.ov] = last;
+    last->second.ov = x.ov;
+    ov_ents.pop_back();
+    ov_dirty = true;
+  }
 };
 #pragma GCC diagnostic pop
 
-static int rs_commit_locked(egm_rstore* r) {
-  if (!r->dirty) return EGM_OK;
+// A full image from `ents` (the live records); the overlay and the tombstones are gone afterwards.
+static int rs_upload_image(egm_rstore* r, const std::vector<Ent*>& ents, uint64_t* h2d) {
   Image im;
-  build_image(r->recs, &im);
+  build_image(ents, &im, &r->by_rank);
   hipError_t e;
   hipStreamSynchronize(r->stream);
   if ((e = put_vec(r->nodes, im.nodes)) || (e = put_vec(r->edges, im.edges)) || (e = put_vec(r->dict, im.dict)) ||
       (e = put_vec(r->dict_blob, im.dict_blob)) || (e = put_vec(r->dict_off, im.dict_off)) ||
       (e = put_vec(r->msg, im.msg)) || (e = put_vec(r->expiry, im.expiry)))
     return r->hip_fail(e, "retained image upload");
+  *h2d += im.nodes.size() * 16 + im.edges.size() * 16 + im.dict.size() * sizeof(DictSlot) + im.dict_blob.size() +
+          im.dict_off.size() * 8 + im.msg.size() * 12;
   r->view.nodes = r->nodes.as<uint4>();
   r->view.edges = r->edges.as<uint4>();
   r->view.edge_mask = im.edge_mask;
@@ -252,7 +305,124 @@ static int rs_commit_locked(egm_rstore* r) {
   r->dtab.dict_blob = r->dict_blob.as<uint8_t>();
   r->dtab.dict_off = r->dict_off.as<uint64_t>();
   r->n_nodes = im.nodes.size();
-  r->dirty = false;
+  r->dead_ranks = 0;
+  r->touched.clear();
+  r->reset = false;
+  return EGM_OK;
+}
+
+// The overlay as one device block: expiry[P] | off[P + 1] | levels[P] | msg[P] | topic bytes.
+static int rs_upload_overlay(egm_rstore* r, uint64_t* h2d) {
+  const size_t P = r->ov_ents.size();
+  uint64_t bytes = 0;
+  for (const Ent* e : r->ov_ents) bytes += e->first.size();
+  if (bytes > 0xFFFFFFF0ull) return r->fail(EGM_E_NOMEM, "overlay topics exceed 4 GiB (lower the overlay cap)");
+  const size_t o_off = P * 8, o_lv = o_off + (P + 1) * 4, o_msg = o_lv + P * 4, o_blob = o_msg + P * 4;
+  std::vector<uint8_t> h(o_blob + bytes);
+  uint64_t* ex = (uint64_t*)h.data();
+  uint32_t* off = (uint32_t*)(h.data() + o_off);
+  uint32_t* lv = (uint32_t*)(h.data() + o_lv);
+  uint32_t* msg = (uint32_t*)(h.data() + o_msg);
+  uint32_t at = 0;
+  for (size_t p = 0; p < P; ++p) {
+    const std::string& t = r->ov_ents[p]->first;
+    const Rec& x = r->ov_ents[p]->second;
+    ex[p] = x.expiry;
+    off[p] = at;
+    lv[p] = 1 + (uint32_t)std::count(t.begin(), t.end(), '/');
+    msg[p] = x.msg;
+    if (!t.empty()) memcpy(h.data() + o_blob + at, t.data(), t.size());
+    at += (uint32_t)t.size();
+  }
+  off[P] = at;
+  hipError_t e;
+  if ((e = r->ovbuf.ensure(h.size() + 16)) ||
+      (e = hipMemcpyAsync(r->ovbuf.p, h.data(), h.size(), hipMemcpyHostToDevice, r->stream)) ||
+      (e = hipStreamSynchronize(r->stream)))   // h is pageable and goes out of scope
+    return r->hip_fail(e, "overlay upload");
+  *h2d += h.size();
+  uint8_t* d = r->ovbuf.as<uint8_t>();
+  r->ov.expiry = (const uint64_t*)d;
+  r->ov.off = (const uint32_t*)(d + o_off);
+  r->ov.levels = (const uint32_t*)(d + o_lv);
+  r->ov.msg = (const uint32_t*)(d + o_msg);
+  r->ov.blob = d + o_blob;
+  r->ov.n = (uint32_t)P;
+  r->ov_dirty = false;
+  return EGM_OK;
+}
+
+// Bring the device up to the host records: patches and tombstones in place,
+// new topics through the overlay.  A rebuild only when asked for, when the
+// overlay outgrew its cap (cap 0: at every change), or when the tombstones
+// outnumber the image's live ranks (the rule of egm_subs_commit).  No match
+// is in flight: the store is one mutex, and a match ends synchronised.
+static int rs_commit_locked(egm_rstore* r, bool force = false) {
+  const bool changed = r->reset || r->ov_dirty || !r->touched.empty();
+  uint64_t dead = r->dead_ranks;
+  for (uint32_t rank : r->touched) {
+    const Rec& x = r->by_rank[rank]->second;
+    dead += (uint64_t)x.dead - (uint64_t)x.dev_dead;
+  }
+  const bool rebuild = force || (changed && r->ov_cap == 0) || r->ov_ents.size() > r->ov_cap ||
+                       dead > r->by_rank.size() - dead;
+  if (!changed && !rebuild) return EGM_OK;
+  uint64_t h2d = 0, patched = 0, tombstoned = 0;
+  int rc;
+  if (rebuild) {
+    std::vector<Ent*> ents;
+    ents.reserve(r->n_live);
+    for (auto it = r->recs.begin(); it != r->recs.end();) {
+      if (it->second.dead) {
+        it = r->recs.erase(it);
+      } else {
+        ents.push_back(&*it);
+        ++it;
+      }
+    }
+    r->ov_ents.clear();
+    if ((rc = rs_upload_image(r, ents, &h2d))) return rc;
+    r->ov.n = 0;
+    r->ov_dirty = false;
+  } else {
+    if (r->reset && (rc = rs_upload_image(r, {}, &h2d))) return rc;   // the empty image: no record is read
+    const size_t k = r->touched.size();
+    if (k) {   // expiry[k] | rank[k] | msg[k], scattered by k_patch on the store's stream
+      std::vector<uint8_t> h(k * 16);
+      uint64_t* ex = (uint64_t*)h.data();
+      uint32_t* idx = (uint32_t*)(h.data() + k * 8);
+      uint32_t* msg = idx + k;
+      for (size_t i = 0; i < k; ++i) {
+        Rec& x = r->by_rank[r->touched[i]]->second;
+        idx[i] = x.rank;
+        ex[i] = x.expiry;
+        msg[i] = x.dead ? RS_TOMB : x.msg;
+        if (!x.dead) ++patched;
+        else if (!x.dev_dead) ++tombstoned;
+        x.dev_dead = x.dead;
+        x.dirty = false;
+      }
+      r->dead_ranks = dead;
+      r->touched.clear();
+      hipError_t e;
+      if ((e = r->pbuf.ensure(h.size()))) return r->hip_fail(e, "retained patch");
+      const uint8_t* d = r->pbuf.as<uint8_t>();
+      const uint32_t* d_idx = (const uint32_t*)(d + k * 8);
+      if ((e = hipMemcpyAsync(r->pbuf.p, h.data(), h.size(), hipMemcpyHostToDevice, r->stream)) ||
+          (e = launch_patch(r->expiry.p, 8, d_idx, d, k, r->stream)) ||
+          (e = launch_patch(r->msg.p, 4, d_idx, d + k * 12, k, r->stream)) ||
+          (e = hipStreamSynchronize(r->stream)))   // h is pageable and goes out of scope
+        return r->hip_fail(e, "retained patch");
+      h2d += h.size();
+    }
+    if (r->ov_dirty && (rc = rs_upload_overlay(r, &h2d))) return rc;
+  }
+  r->last.rebuilt = rebuild ? 1 : 0;
+  r->last.patched = patched;
+  r->last.tombstoned = tombstoned;
+  r->last.overlay = r->ov_ents.size();
+  r->last.dead = r->dead_ranks;
+  r->last.h2d = h2d;
   return EGM_OK;
 }
 
@@ -301,17 +471,40 @@ const char* egm_rstore_last_error(egm_rstore* r) { return r ? r->err.c_str() : "
 
 int egm_rstore_put(egm_rstore* r, const uint8_t* topic, uint32_t len, uint32_t msg_id, uint64_t expiry_ms) {
   if (!r || (!topic && len)) return EGM_E_INVAL;
+  if (msg_id == RS_TOMB) return EGM_E_INVAL;               // the image's tombstone mark
   if (has_wildcard_word(topic, len)) return EGM_E_INVAL;   // publish topics carry no wildcard
   std::lock_guard<std::mutex> g(r->mu);
-  r->recs[std::string((const char*)topic, len)] = Rec{msg_id, expiry_ms};
-  r->dirty = true;
+  auto [it, fresh] = r->recs.try_emplace(std::string((const char*)topic, len));
+  Rec& x = it->second;
+  if (fresh) {                       // not in the image: the overlay
+    x.ov = (uint32_t)r->ov_ents.size();
+    r->ov_ents.push_back(&*it);
+    ++r->n_live;
+  } else if (x.rank != NONE) {       // patch the rank; a tombstoned one comes back
+    if (x.dead) ++r->n_live;
+    x.dead = false;
+    r->touch(x);
+  }
+  if (x.rank == NONE) r->ov_dirty = true;
+  x.msg = msg_id;
+  x.expiry = expiry_ms;
   return EGM_OK;
 }
 
 int egm_rstore_delete(egm_rstore* r, const uint8_t* topic, uint32_t len) {
   if (!r || (!topic && len)) return EGM_E_INVAL;
   std::lock_guard<std::mutex> g(r->mu);
-  r->dirty |= r->recs.erase(std::string((const char*)topic, len)) > 0;
+  auto it = r->recs.find(std::string((const char*)topic, len));
+  if (it == r->recs.end() || it->second.dead) return EGM_OK;
+  Rec& x = it->second;
+  --r->n_live;
+  if (x.rank != NONE) {
+    x.dead = true;
+    r->touch(x);
+  } else {
+    r->ov_remove(x);
+    r->recs.erase(it);
+  }
   return EGM_OK;
 }
 
@@ -319,14 +512,18 @@ int egm_rstore_clean(egm_rstore* r) {
   if (!r) return EGM_E_INVAL;
   std::lock_guard<std::mutex> g(r->mu);
   r->recs.clear();
-  r->dirty = true;
+  r->by_rank.clear();
+  r->ov_ents.clear();
+  r->touched.clear();
+  r->n_live = r->dead_ranks = 0;
+  r->reset = r->ov_dirty = true;
   return EGM_OK;
 }
 
 int egm_rstore_size(egm_rstore* r, uint64_t* n) {
   if (!r || !n) return EGM_E_INVAL;
   std::lock_guard<std::mutex> g(r->mu);
-  *n = r->recs.size();
+  *n = r->n_live;
   return EGM_OK;
 }
 
@@ -335,6 +532,80 @@ int egm_rstore_commit(egm_rstore* r) {
   std::lock_guard<std::mutex> g(r->mu);
   if (hipSetDevice(r->device) != hipSuccess) return EGM_E_DEVICE;
   return rs_commit_locked(r);
+}
+
+int egm_rstore_rebuild(egm_rstore* r) {
+  if (!r) return EGM_E_INVAL;
+  std::lock_guard<std::mutex> g(r->mu);
+  if (hipSetDevice(r->device) != hipSuccess) return EGM_E_DEVICE;
+  return rs_commit_locked(r, true);
+}
+
+int egm_rstore_set_overlay_cap(egm_rstore* r, uint32_t max_topics) {
+  if (!r) return EGM_E_INVAL;
+  std::lock_guard<std::mutex> g(r->mu);
+  r->ov_cap = max_topics;
+  return EGM_OK;
+}
+
+int egm_rstore_last_commit(egm_rstore* r, int* rebuilt, uint64_t* patched, uint64_t* tombstoned,
+                           uint64_t* overlay_topics, uint64_t* dead_ranks, uint64_t* h2d_bytes) {
+  if (!r || !rebuilt || !patched || !tombstoned || !overlay_topics || !dead_ranks || !h2d_bytes) return EGM_E_INVAL;
+  std::lock_guard<std::mutex> g(r->mu);
+  *rebuilt = r->last.rebuilt;
+  *patched = r->last.patched;
+  *tombstoned = r->last.tombstoned;
+  *overlay_topics = r->last.overlay;
+  *dead_ranks = r->last.dead;
+  *h2d_bytes = r->last.h2d;
+  return EGM_OK;
+}
+
+int egm_rstore_clear_expired(egm_rstore* r, uint64_t now_ms, uint32_t** msg_ids, uint64_t* n) {
+  if (!r || !msg_ids || !n) return EGM_E_INVAL;
+  *msg_ids = nullptr;
+  *n = 0;
+  std::lock_guard<std::mutex> g(r->mu);
+  if (hipSetDevice(r->device) != hipSuccess) return EGM_E_DEVICE;
+  int rc = rs_commit_locked(r);   // the device's expiry[] and tombstones are the records'
+  if (rc) return rc;
+  hipStream_t s = r->stream;
+  hipError_t e;
+  const uint32_t M = r->view.n_topics;
+  uint32_t k = 0;
+  std::vector<uint32_t> ranks;
+  if ((e = r->xout.ensure((size_t)M * 4 + 16)) || (e = r->xn.ensure(16)) ||
+      (e = launch_rs_expire(r->expiry.as<uint64_t>(), r->msg.as<uint32_t>(), M, now_ms, r->xout.as<uint32_t>(),
+                            r->xn.as<uint32_t>(), s)) ||
+      (e = hipMemcpyAsync(&k, r->xn.p, 4, hipMemcpyDeviceToHost, s)) || (e = hipStreamSynchronize(s)))
+    return r->hip_fail(e, "expire");
+  ranks.resize(k);
+  if (k && ((e = hipMemcpyAsync(ranks.data(), r->xout.p, (size_t)k * 4, hipMemcpyDeviceToHost, s)) ||
+            (e = hipStreamSynchronize(s))))
+    return r->hip_fail(e, "expire readback");
+  std::vector<uint32_t> gone;
+  gone.reserve(k);
+  for (uint32_t rank : ranks) {      // the kernel made these ranks tombstones
+    Rec& x = r->by_rank[rank]->second;
+    gone.push_back(x.msg);
+    x.dead = x.dev_dead = true;
+  }
+  r->dead_ranks += k;
+  for (size_t p = r->ov_ents.size(); p-- > 0;) {   // the overlay, on the host
+    Ent* en = r->ov_ents[p];
+    if (en->second.expiry == 0 || en->second.expiry >= now_ms) continue;
+    gone.push_back(en->second.msg);
+    r->ov_remove(en->second);
+    r->recs.erase(r->recs.find(en->first));
+  }
+  r->n_live -= gone.size();
+  if (gone.empty()) return EGM_OK;
+  uint32_t* mem = (uint32_t*)result_alloc(gone.size() * 4);
+  if (!mem) return r->fail(EGM_E_NOMEM, "result");
+  memcpy(mem, gone.data(), gone.size() * 4);
+  *msg_ids = mem;
+  *n = gone.size();
+  return EGM_OK;
 }
 
 int egm_rstore_match(egm_rstore* r, const uint8_t* blob, const uint32_t* off, uint32_t n, uint64_t now_ms, int mode,
@@ -441,12 +712,20 @@ int egm_rstore_match(egm_rstore* r, const uint8_t* blob, const uint32_t* off, ui
     if (attempt == 1) return r->fail(EGM_E_NOMEM, "ranges capacity");
   }
   uint64_t* d_row = r->row.as<uint64_t>();
-  if ((e = launch_rs_rows(w, n_ranges, n, d_row, s))) return r->hip_fail(e, "rows");
+  RetainOverlay ov = r->ov;   // one mask and base per (filter, tile of 64 overlay topics)
+  const uint64_t ov_pairs = (uint64_t)n * ((ov.n + 63) / 64);
+  if ((e = r->ovmask.ensure(ov_pairs * 8 + 16)) || (e = r->ovbase.ensure(ov_pairs * 4 + 16)))
+    return r->hip_fail(e, "overlay workspace");
+  ov.mask = r->ovmask.as<uint64_t>();
+  ov.base = r->ovbase.as<uint32_t>();
+  if ((e = launch_rs_rows(w, ov, r->in_blob.as<uint8_t>(), n_ranges, n, d_row, s))) return r->hip_fail(e, "rows");
   uint64_t total = 0;
   if ((e = hipMemcpyAsync(&total, d_row + n, 8, hipMemcpyDeviceToHost, s)) || (e = hipStreamSynchronize(s)))
     return r->hip_fail(e, "rows readback");
   if ((e = r->ids.ensure(total * 4 + 16))) return r->hip_fail(e, "ids");
-  if ((e = launch_rs_expand(r->view, w, n_ranges, d_row, r->ids.as<uint32_t>(), s))) return r->hip_fail(e, "expand");
+  if ((e = launch_rs_expand(r->view, w, n_ranges, d_row, r->ids.as<uint32_t>(), s)) ||
+      (e = launch_rs_ov_fill(ov, n, d_row, r->ids.as<uint32_t>(), s)))
+    return r->hip_fail(e, "expand");
 
   size_t sz = sizeof(egm_result);
   const size_t o_counts = sz;

@@ -9,7 +9,9 @@ or, for a plain topic, the record of that topic (``read_messages/1``
 (``apps/emqx_retainer/src/emqx_retainer.erl:107-117``).  The matching runs in
 the C-ABI library (``egm_rstore_*``): a word trie of the stored topics in HBM,
 walked level by level for a whole batch of filters at once.  Messages stay on
-the host; the device holds topic -> message-id records.
+the host; the device holds topic -> message-id records.  Puts and deletes are
+applied incrementally (patches, tombstones, an overlay of new topics; DESIGN
+§4.3), and ``clear_expired/1`` (:103-112) runs on the device.
 """
 from __future__ import annotations
 
@@ -93,7 +95,42 @@ class RetainedStore:
         return n.value
 
     def commit(self):
+        """Apply the puts and deletes made so far (the next lookup would):
+        patches, tombstones and the overlay; a rebuild only when needed."""
         self._check(self.lib.egm_rstore_commit(self.h), "egm_rstore_commit")
+
+    def rebuild(self):
+        """A full device image from the records; empties the overlay."""
+        self._check(self.lib.egm_rstore_rebuild(self.h), "egm_rstore_rebuild")
+
+    def set_overlay_cap(self, n: int):
+        """Topics the overlay may hold before a commit rebuilds (0: every commit does)."""
+        self._check(self.lib.egm_rstore_set_overlay_cap(self.h, n), "egm_rstore_set_overlay_cap")
+
+    def last_commit(self) -> Dict[str, int]:
+        """What the last commit that had changes to apply did."""
+        rebuilt = C.c_int()
+        v = [C.c_uint64() for _ in range(5)]
+        self._check(self.lib.egm_rstore_last_commit(self.h, C.byref(rebuilt), *[C.byref(x) for x in v]),
+                    "egm_rstore_last_commit")
+        names = ("patched", "tombstoned", "overlay_topics", "dead_ranks", "h2d_bytes")
+        return {"rebuilt": rebuilt.value, **{k: x.value for k, x in zip(names, v)}}
+
+    def clear_expired(self, now: int) -> List[int]:
+        """``clear_expired/1`` (:103-112): every record with ``0 < expiry < now``
+        is deleted; returns the ids of the dropped messages."""
+        ids = L._u32p()
+        n = C.c_uint64()
+        self._check(self.lib.egm_rstore_clear_expired(self.h, now, C.byref(ids), C.byref(n)),
+                    "egm_rstore_clear_expired")
+        try:
+            gone = [int(ids[i]) for i in range(n.value)]
+        finally:
+            self.lib.egm_result_free(ids)
+        for mid in gone:
+            topic = self._msgs.pop(mid)[0]
+            del self._by_topic[topic]
+        return gone
 
     # -- lookups ----------------------------------------------------------------
     def match_ids(self, filters: Sequence[bytes], now: int, mode: int = L.EGM_RMODE_DISPATCH) -> List[np.ndarray]:

@@ -406,9 +406,14 @@ void egm_result_free(void* result);
    One subscription filter against every stored retained topic, for a batch of
    filters.  Replaces apps/emqx_retainer/src/emqx_retainer_mnesia.erl:
      egm_rstore_put     <- store_retained/2  :73-101 (one record per topic;
-                           topics with a '+'/'#' word are rejected: EGM_E_INVAL)
+                           topics with a '+'/'#' word are rejected: EGM_E_INVAL,
+                           and so is the message id 0xFFFFFFFF, which marks a
+                           deleted topic inside the device image)
      egm_rstore_delete  <- delete_message/2  :114-129 (plain topic)
      egm_rstore_clean   <- clean/1           :148-150
+     egm_rstore_clear_expired <- clear_expired/1 :103-112 (the timer of
+                           apps/emqx_retainer/src/emqx_retainer.erl:209-213):
+                           every record with 0 < expiry < now_ms is deleted
      egm_rstore_match   <- match_messages/1  :200-204 with condition/1 :215-220
                            and make_match_spec/1 :222-228: '+' matches any one
                            word, a last '#' any rest (also none), NO '$' rule;
@@ -419,7 +424,17 @@ void egm_result_free(void* result);
                            (apps/emqx_retainer/src/emqx_retainer.erl:107-117).
    Result rows hold message ids (order within a row unspecified: the reference
    sorts by timestamp, sort_retained/1 :154-159, on the host).  Changes are
-   visible to the next match (the device image is rebuilt on demand). */
+   visible to the next match, which commits them first.
+
+   A commit is incremental.  The device holds an image of the topics (a word
+   trie with ranked topics) and an overlay.  A put on a topic of the image
+   patches its message id and expiry in place; a delete turns its rank into a
+   tombstone, which a later put of that topic revives; a topic the image does
+   not hold goes into the overlay, a short list matched on its bytes.  The image
+   is rebuilt from the records only by egm_rstore_rebuild, when the overlay
+   would hold more than its cap (4096 topics unless set), or when tombstones
+   outnumber the image's live topics.  egm_rstore_clean drops the image; the
+   topics stored after it start a new overlay, as in a new store. */
 typedef struct egm_rstore egm_rstore;
 enum { EGM_RMODE_MATCH = 0, EGM_RMODE_DISPATCH = 1 };
 int egm_rstore_open(int device, egm_rstore** out);
@@ -429,8 +444,25 @@ int egm_rstore_put(egm_rstore* rs, const uint8_t* topic, uint32_t len, uint32_t 
 int egm_rstore_delete(egm_rstore* rs, const uint8_t* topic, uint32_t len);
 int egm_rstore_clean(egm_rstore* rs);
 int egm_rstore_size(egm_rstore* rs, uint64_t* n);
-/* Upload the current records now (otherwise done by the next match). */
+/* Apply the changes now (otherwise done by the next match). */
 int egm_rstore_commit(egm_rstore* rs);
+/* A full image from the records; empties the overlay and the tombstones
+   (what every commit did before commits were incremental). */
+int egm_rstore_rebuild(egm_rstore* rs);
+/* Topics the overlay may hold before a commit rebuilds; 0 = every commit that
+   changes anything rebuilds (the old behaviour). */
+int egm_rstore_set_overlay_cap(egm_rstore* rs, uint32_t max_topics);
+/* The last commit that had something to apply: whether it rebuilt the image,
+   ranks patched (message id and expiry) and ranks newly tombstoned, the
+   overlay's topics and the image's tombstones after it, bytes uploaded.
+   Every out pointer is required. */
+int egm_rstore_last_commit(egm_rstore* rs, int* rebuilt, uint64_t* patched, uint64_t* tombstoned,
+                           uint64_t* overlay_topics, uint64_t* dead_ranks, uint64_t* h2d_bytes);
+/* <- clear_expired/1 :103-112.  Deletes every record with 0 < expiry < now_ms
+   (one device pass over the image's expiries; the overlay on the host) and
+   returns their message ids: *msg_ids (NULL when *n == 0) is freed with
+   egm_result_free. */
+int egm_rstore_clear_expired(egm_rstore* rs, uint64_t now_ms, uint32_t** msg_ids, uint64_t* n);
 int egm_rstore_match(egm_rstore* rs, const uint8_t* filters_blob, const uint32_t* offsets, uint32_t n,
                      uint64_t now_ms, int mode, egm_result** out);
 

@@ -12,6 +12,13 @@ of the filters; its counts are checked against the GPU rows.
 
     python tools/bench_retained.py [--topics 1000000] [--filters 100000]
 One JSON line on stdout.
+
+--churn K measures the live store instead, in one process on
+the same store: the time of egm_rstore_rebuild; then, with the overlay holding
+0, 256, 1024, 4096 and 16384 topics, the match of the filter batch, the commit
+of K puts (half on topics of the image, half new) and the match after it; and
+the same K puts committed with the overlay cap at 0, where a commit is a
+rebuild.  One JSON line on stdout (bench "retained_live").
 """
 import argparse
 import json
@@ -31,6 +38,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
+    ap.add_argument("--churn", type=int, default=0, metavar="K",
+                    help="measure rebuild, incremental commit of K changes and match against the overlay")
     a = ap.parse_args()
     from emqx_amd import _lib as L
     from emqx_amd import synth
@@ -72,6 +81,11 @@ def main():
         lib.egm_result_free(res)
         return tot, counts
 
+    if a.churn:
+        churn(a, rs, step, topics, flt, build_s)
+        rs.close()
+        return
+
     step()
     ts = []
     for _ in range(a.steps):
@@ -105,6 +119,96 @@ def main():
     }
     print(json.dumps(out))
     rs.close()
+
+
+OVERLAY_SIZES = (0, 256, 1024, 4096, 16384)
+
+
+def churn(a, rs, step, topics, flt, build_s):
+    """The live store: rebuild, incremental commits and overlay matches (--churn)."""
+    from emqx_amd import synth
+
+    lib, h = rs.lib, rs.h
+    K = a.churn
+    c = synth.CONFIGS["c2"]
+    seed = synth.SEED_BASE + synth.CONFIG_INDEX["c2"]
+    have = set(topics)
+    need = max(OVERLAY_SIZES) + 8 * K
+    extra = synth.topics(2 * need + 1000, flt, c["dmin"], c["dmax"], seed=seed + 18)   # shaped like the stored ones
+    pool = [x for x in dict.fromkeys(extra.to_list())
+            if x not in have and b"+" not in x.split(b"/") and b"#" not in x.split(b"/")]
+    assert len(pool) >= need, (len(pool), need)
+    next_id = [len(topics)]
+    rng = np.random.default_rng(5)
+
+    def put(t):
+        assert lib.egm_rstore_put(h, t, len(t), next_id[0], 0) == 0
+        next_id[0] += 1
+
+    def timed(fn, reps=1):
+        ts = []
+        for _ in range(reps):
+            t1 = time.perf_counter()
+            r = fn()
+            ts.append(time.perf_counter() - t1)
+        return 1e3 * float(np.median(ts)), r
+
+    def changes():
+        """K puts: half on topics of the image, half new; returns the new ones."""
+        new = [pool.pop() for _ in range(K - K // 2)]
+        for i in rng.choice(len(topics), K // 2, replace=False):
+            put(topics[int(i)])
+        for t in new:
+            put(t)
+        return new
+
+    step()                                    # warm: code objects, workspace
+    rebuild_ms, _ = timed(rs.rebuild, 2)
+    rows = []
+    rs.set_overlay_cap(1 << 20)               # the sizes below are set by hand
+    overlay = []
+    for size in OVERLAY_SIZES:
+        while len(overlay) < size:
+            overlay.append(pool.pop())
+            put(overlay[-1])
+        rs.commit()
+        st = rs.last_commit() if size else {"rebuilt": 0, "overlay_topics": 0}
+        assert st["rebuilt"] == 0 and st["overlay_topics"] == size, st
+        step()
+        match_ms, (tot, _) = timed(step, a.steps)
+        new = changes()
+        commit_ms, _ = timed(rs.commit)
+        st = rs.last_commit()
+        assert st["rebuilt"] == 0 and st["patched"] == K // 2 and st["overlay_topics"] == size + len(new), st
+        after_ms, (tot2, _) = timed(step)
+        assert tot2 >= tot, (tot, tot2)       # topics were added, none removed
+        for t in new:                         # back to `size` overlay topics
+            assert lib.egm_rstore_delete(h, t, len(t)) == 0
+        rows.append({"overlay_topics": size, "match_ms": match_ms, "commit_ms": commit_ms,
+                     "match_after_commit_ms": after_ms, "h2d_bytes": st["h2d_bytes"], "matched_ids": tot})
+        print(f"overlay {size}: match {match_ms:.2f} ms, commit of {K} {commit_ms:.3f} ms, "
+              f"match after {after_ms:.2f} ms", file=sys.stderr, flush=True)
+    # cap 0: the same kind of change, committed by a rebuild
+    rs.set_overlay_cap(0)
+    rs.rebuild()
+    changes()
+    full_ms, _ = timed(rs.commit)
+    st = rs.last_commit()
+    assert st["rebuilt"] == 1, st
+    full_after_ms, _ = timed(step)
+    inc_ms = rows[0]["commit_ms"]
+    out = {
+        "bench": "retained_live", "metric": "commit of K changes to the retained store, incremental vs rebuild",
+        "value": full_ms / inc_ms, "unit": "x (cap-0 commit time / incremental commit time, overlay 0)",
+        "config": {"workload": "c2-shaped", "stored_topics": len(topics), "filters_per_batch": a.filters,
+                   "changes_per_commit": K, "mix": "half puts on image topics, half new topics"},
+        "rebuild_ms": rebuild_ms, "store_build_s": build_s, "by_overlay_size": rows,
+        "cap0": {"commit_ms": full_ms, "match_after_commit_ms": full_after_ms, "h2d_bytes": st["h2d_bytes"]},
+        "match_ratio_4096_vs_0": rows[3]["match_ms"] / rows[0]["match_ms"],
+        "incremental_commit_faster": bool(max(r["commit_ms"] for r in rows) < full_ms),
+    }
+    print(json.dumps(out))
+    assert out["incremental_commit_faster"], "the incremental commit is not faster than the cap-0 commit"
 
 
 if __name__ == "__main__":
