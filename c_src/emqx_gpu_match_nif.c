@@ -28,6 +28,23 @@
  *                      (emqx_broker.erl:200-209, 283-308) for a list of topics;
  *                      returns [{[FilterId], [{FilterId, Sub}]}]
  *
+ * The retained store (apps/emqx_retainer/src/emqx_retainer_mnesia.erl), a
+ * resource of its own beside the route context:
+ *   rs_open/1            -> egm_rstore_open
+ *   rs_put/4             -> egm_rstore_put           (store_retained/2 :73-101;
+ *                           {error, full} is is_table_full/0's refusal :92-97)
+ *   rs_delete/2          -> egm_rstore_delete        (delete_message/2, plain topic :117-127)
+ *   rs_delete_matching/2 -> egm_rstore_delete_matching (delete_message/2 with
+ *                           wildcard filters :114-116, 206-212; returns the dropped ids)
+ *   rs_set_max_retained/2 -> egm_rstore_set_max_retained (max_retained_messages :230-240)
+ *   rs_clean/1           -> egm_rstore_clean         (clean/1 :148-150)
+ *   rs_size/1            -> egm_rstore_size          (table_size/0 :238-240)
+ *   rs_commit/1          -> egm_rstore_commit
+ *   rs_clear_expired/2   -> egm_rstore_clear_expired (clear_expired/1 :103-112; NowMs is passed in)
+ *   rs_match/4           -> egm_rstore_match         (match_messages/1 :200-204, or, Mode 1,
+ *                           read_messages/1 :187-198 for plain topics; returns [[MsgId]])
+ * Messages stay in Erlang: the store maps a topic to the caller's message id.
+ *
  * Threading: match_batch and apply_delta run on dirty CPU schedulers
  * (ERL_NIF_DIRTY_JOB_CPU_BOUND) — a batch takes well over 1 ms.  The library
  * serialises calls per context.  Inputs (Erlang binaries) are borrowed only
@@ -49,6 +66,11 @@ typedef struct {
 
 static ErlNifResourceType* EGM_RES;
 static ErlNifResourceType* EGM_TICKET;
+static ErlNifResourceType* EGM_RSTORE;
+
+typedef struct {
+  egm_rstore* rs;
+} egm_rs_t;
 
 /* A submitted batch: keeps its context alive until it is waited or cancelled. */
 typedef struct {
@@ -56,7 +78,7 @@ typedef struct {
   uint64_t ticket;
   int live;           /* not yet waited or cancelled */
 } egm_ticket_t;
-static ERL_NIF_TERM ATOM_OK, ATOM_ERROR;
+static ERL_NIF_TERM ATOM_OK, ATOM_ERROR, ATOM_FULL;
 
 static void egm_res_dtor(ErlNifEnv* env, void* obj) {
   (void)env;
@@ -74,6 +96,13 @@ static void egm_ticket_dtor(ErlNifEnv* env, void* obj) {
   t->owner = NULL;
 }
 
+static void egm_rs_dtor(ErlNifEnv* env, void* obj) {
+  (void)env;
+  egm_rs_t* r = (egm_rs_t*)obj;
+  if (r->rs) egm_rstore_close(r->rs);
+  r->rs = NULL;
+}
+
 static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
   (void)priv;
   (void)info;
@@ -81,9 +110,12 @@ static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
                                     ERL_NIF_RT_CREATE | ERL_NIF_RT_TAKEOVER, NULL);
   EGM_TICKET = enif_open_resource_type(env, NULL, "emqx_gpu_match_ticket", egm_ticket_dtor,
                                        ERL_NIF_RT_CREATE | ERL_NIF_RT_TAKEOVER, NULL);
+  EGM_RSTORE = enif_open_resource_type(env, NULL, "emqx_gpu_match_rstore", egm_rs_dtor,
+                                       ERL_NIF_RT_CREATE | ERL_NIF_RT_TAKEOVER, NULL);
   ATOM_OK = enif_make_atom(env, "ok");
   ATOM_ERROR = enif_make_atom(env, "error");
-  return (EGM_RES && EGM_TICKET) ? 0 : -1;
+  ATOM_FULL = enif_make_atom(env, "full");
+  return (EGM_RES && EGM_TICKET && EGM_RSTORE) ? 0 : -1;
 }
 
 static ERL_NIF_TERM error_tuple(ErlNifEnv* env, egm_ctx* ctx, int rc) {
@@ -427,6 +459,154 @@ static ERL_NIF_TERM nif_publish_batch(ErlNifEnv* env, int argc, const ERL_NIF_TE
   return enif_make_tuple2(env, ATOM_OK, out);
 }
 
+/* ---- retained store ---- */
+static ERL_NIF_TERM rs_error(ErlNifEnv* env, egm_rstore* rs, int rc) {
+  const char* msg = rs ? egm_rstore_last_error(rs) : "egm error";
+  return enif_make_tuple2(env, ATOM_ERROR,
+                          enif_make_tuple2(env, enif_make_int(env, rc), enif_make_string(env, msg, ERL_NIF_LATIN1)));
+}
+
+static int get_rs(ErlNifEnv* env, ERL_NIF_TERM t, egm_rs_t** r) {
+  return enif_get_resource(env, t, EGM_RSTORE, (void**)r) && (*r)->rs;
+}
+
+/* [MsgId] from ids[n] */
+static ERL_NIF_TERM ids_term(ErlNifEnv* env, const uint32_t* ids, uint64_t n) {
+  ERL_NIF_TERM list = enif_make_list(env, 0);
+  for (uint64_t k = n; k-- > 0;) list = enif_make_list_cell(env, enif_make_uint(env, ids[k]), list);
+  return list;
+}
+
+/* rs_open(Device :: non_neg_integer()) -> {ok, Store} | {error, _} */
+static ERL_NIF_TERM nif_rs_open(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  int dev;
+  if (argc != 1 || !enif_get_int(env, argv[0], &dev) || dev < 0) return enif_make_badarg(env);
+  egm_rstore* rs = NULL;
+  int rc = egm_rstore_open(dev, &rs);
+  if (rc) return rs_error(env, NULL, rc);
+  egm_rs_t* r = (egm_rs_t*)enif_alloc_resource(EGM_RSTORE, sizeof(egm_rs_t));
+  r->rs = rs;
+  ERL_NIF_TERM term = enif_make_resource(env, r);
+  enif_release_resource(r);
+  return enif_make_tuple2(env, ATOM_OK, term);
+}
+
+/* rs_put(Store, Topic :: binary(), MsgId, ExpiryMs) -> ok | {error, full} | {error, _}
+   (0 =< MsgId < 16#FFFFFFFF; ExpiryMs 0 = never) */
+static ERL_NIF_TERM nif_rs_put(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_rs_t* r;
+  ErlNifBinary topic;
+  unsigned id;
+  ErlNifUInt64 expiry;
+  if (argc != 4 || !get_rs(env, argv[0], &r) || !enif_inspect_binary(env, argv[1], &topic) ||
+      topic.size > 0xFFFFFFFFu || !enif_get_uint(env, argv[2], &id) || !enif_get_uint64(env, argv[3], &expiry))
+    return enif_make_badarg(env);
+  int rc = egm_rstore_put(r->rs, topic.data, (uint32_t)topic.size, id, expiry);
+  if (rc == EGM_E_FULL) return enif_make_tuple2(env, ATOM_ERROR, ATOM_FULL);
+  return rc ? rs_error(env, r->rs, rc) : ATOM_OK;
+}
+
+/* rs_delete(Store, Topic :: binary()) -> ok | {error, _}: the topic itself, no wildcard */
+static ERL_NIF_TERM nif_rs_delete(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_rs_t* r;
+  ErlNifBinary topic;
+  if (argc != 2 || !get_rs(env, argv[0], &r) || !enif_inspect_binary(env, argv[1], &topic) ||
+      topic.size > 0xFFFFFFFFu)
+    return enif_make_badarg(env);
+  int rc = egm_rstore_delete(r->rs, topic.data, (uint32_t)topic.size);
+  return rc ? rs_error(env, r->rs, rc) : ATOM_OK;
+}
+
+/* rs_delete_matching(Store, [Filter :: binary()]) -> {ok, [MsgId]} | {error, _} */
+static ERL_NIF_TERM nif_rs_delete_matching(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_rs_t* r;
+  uint8_t* blob;
+  uint32_t *off, n;
+  if (argc != 2 || !get_rs(env, argv[0], &r) || !pack_list(env, argv[1], &blob, &off, &n))
+    return enif_make_badarg(env);
+  uint32_t* ids = NULL;
+  uint64_t n_ids = 0;
+  int rc = egm_rstore_delete_matching(r->rs, blob, off, n, &ids, &n_ids);
+  free(blob);
+  free(off);
+  if (rc) return rs_error(env, r->rs, rc);
+  ERL_NIF_TERM list = ids_term(env, ids, n_ids);
+  egm_result_free(ids);
+  return enif_make_tuple2(env, ATOM_OK, list);
+}
+
+/* rs_set_max_retained(Store, Max) -> ok | {error, _}: max_retained_messages; 0 = no limit */
+static ERL_NIF_TERM nif_rs_set_max_retained(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_rs_t* r;
+  ErlNifUInt64 max;
+  if (argc != 2 || !get_rs(env, argv[0], &r) || !enif_get_uint64(env, argv[1], &max)) return enif_make_badarg(env);
+  int rc = egm_rstore_set_max_retained(r->rs, max);
+  return rc ? rs_error(env, r->rs, rc) : ATOM_OK;
+}
+
+/* rs_clean(Store) -> ok | {error, _} */
+static ERL_NIF_TERM nif_rs_clean(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_rs_t* r;
+  if (argc != 1 || !get_rs(env, argv[0], &r)) return enif_make_badarg(env);
+  int rc = egm_rstore_clean(r->rs);
+  return rc ? rs_error(env, r->rs, rc) : ATOM_OK;
+}
+
+/* rs_size(Store) -> {ok, non_neg_integer()} | {error, _} */
+static ERL_NIF_TERM nif_rs_size(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_rs_t* r;
+  if (argc != 1 || !get_rs(env, argv[0], &r)) return enif_make_badarg(env);
+  uint64_t n = 0;
+  int rc = egm_rstore_size(r->rs, &n);
+  return rc ? rs_error(env, r->rs, rc) : enif_make_tuple2(env, ATOM_OK, enif_make_uint64(env, n));
+}
+
+/* rs_commit(Store) -> ok | {error, _}: apply the puts and deletes now (the next lookup would) */
+static ERL_NIF_TERM nif_rs_commit(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_rs_t* r;
+  if (argc != 1 || !get_rs(env, argv[0], &r)) return enif_make_badarg(env);
+  int rc = egm_rstore_commit(r->rs);
+  return rc ? rs_error(env, r->rs, rc) : ATOM_OK;
+}
+
+/* rs_clear_expired(Store, NowMs) -> {ok, [MsgId]} | {error, _} */
+static ERL_NIF_TERM nif_rs_clear_expired(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_rs_t* r;
+  ErlNifUInt64 now;
+  if (argc != 2 || !get_rs(env, argv[0], &r) || !enif_get_uint64(env, argv[1], &now)) return enif_make_badarg(env);
+  uint32_t* ids = NULL;
+  uint64_t n_ids = 0;
+  int rc = egm_rstore_clear_expired(r->rs, now, &ids, &n_ids);
+  if (rc) return rs_error(env, r->rs, rc);
+  ERL_NIF_TERM list = ids_term(env, ids, n_ids);
+  egm_result_free(ids);
+  return enif_make_tuple2(env, ATOM_OK, list);
+}
+
+/* rs_match(Store, [Filter :: binary()], NowMs, Mode :: 0 | 1) -> {ok, [[MsgId]]} | {error, _} */
+static ERL_NIF_TERM nif_rs_match(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_rs_t* r;
+  ErlNifUInt64 now;
+  int mode;
+  uint8_t* blob;
+  uint32_t *off, n;
+  if (argc != 4 || !get_rs(env, argv[0], &r) || !enif_get_uint64(env, argv[2], &now) ||
+      !enif_get_int(env, argv[3], &mode) || (mode != EGM_RMODE_MATCH && mode != EGM_RMODE_DISPATCH) ||
+      !pack_list(env, argv[1], &blob, &off, &n))
+    return enif_make_badarg(env);
+  egm_result* res = NULL;
+  int rc = egm_rstore_match(r->rs, blob, off, n, now, mode, &res);
+  free(blob);
+  free(off);
+  if (rc) {
+    if (res) egm_result_free(res);
+    return rs_error(env, r->rs, rc);
+  }
+  ERL_NIF_TERM rows = rows_term(env, res);
+  egm_result_free(res);
+  return enif_make_tuple2(env, ATOM_OK, rows);
+}
+
 static ErlNifFunc nif_funcs[] = {
     {"open", 1, nif_open, 0},
     {"build", 2, nif_build, ERL_NIF_DIRTY_JOB_CPU_BOUND},
@@ -438,6 +618,18 @@ static ErlNifFunc nif_funcs[] = {
     {"subs_build", 2, nif_subs_build, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"subs_delta", 3, nif_subs_delta, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"publish_batch", 2, nif_publish_batch, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    /* the retained store: every call takes the store's lock, which a match or a
+       delete holds across its device work, so none runs on a normal scheduler */
+    {"rs_open", 1, nif_rs_open, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"rs_put", 4, nif_rs_put, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"rs_delete", 2, nif_rs_delete, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"rs_delete_matching", 2, nif_rs_delete_matching, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"rs_set_max_retained", 2, nif_rs_set_max_retained, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"rs_clean", 1, nif_rs_clean, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"rs_size", 1, nif_rs_size, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"rs_commit", 1, nif_rs_commit, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"rs_clear_expired", 2, nif_rs_clear_expired, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"rs_match", 4, nif_rs_match, ERL_NIF_DIRTY_JOB_CPU_BOUND},
 };
 
 ERL_NIF_INIT(emqx_gpu_match, nif_funcs, load, NULL, NULL, NULL)

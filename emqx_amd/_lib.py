@@ -19,6 +19,7 @@ EGM_E_DEVICE = -3
 EGM_E_OVERFLOW = -4
 EGM_E_STATE = -5
 EGM_E_NOTFOUND = -6
+EGM_E_FULL = -7
 
 EGM_MODE_TRIE = 0
 EGM_MODE_ROUTES = 1
@@ -144,6 +145,8 @@ SIGNATURES = {
     "egm_rstore_set_overlay_cap": (C.c_int, [_P, C.c_uint32]),
     "egm_rstore_last_commit": (C.c_int, [_P, C.POINTER(C.c_int), _u64p, _u64p, _u64p, _u64p, _u64p]),
     "egm_rstore_clear_expired": (C.c_int, [_P, C.c_uint64, C.POINTER(_u32p), _u64p]),
+    "egm_rstore_delete_matching": (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(_u32p), _u64p]),
+    "egm_rstore_set_max_retained": (C.c_int, [_P, C.c_uint64]),
     "egm_rstore_match": (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint64, C.c_int,
                                    C.POINTER(C.POINTER(egm_result))]),
     "egm_image_new": (_P, []),

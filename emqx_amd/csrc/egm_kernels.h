@@ -328,5 +328,16 @@ hipError_t launch_rs_ov_fill(const RetainOverlay& o, uint32_t n, const uint64_t*
 // clear_expired/1: tombstones the image ranks with 0 < expiry < now, appends them to out[m], *n_out = how many
 hipError_t launch_rs_expire(const uint64_t* expiry, uint32_t* msg, uint32_t m, uint64_t now, uint32_t* out,
                             uint32_t* n_out, hipStream_t s);
+// delete_message/2 with filters (match_delete_messages/1 :206-212).  The
+// overlay's (filter, tile) masks alone, without the rows: o.mask as
+// launch_rs_rows leaves it; w.fcnt[n + 1] is scratch.
+hipError_t launch_rs_ov_masks(const RetainWork& w, const RetainOverlay& o, const uint8_t* fblob, uint32_t n,
+                              hipStream_t s);
+// The image: len[nr] = ranks per emitted range, koff[nr + 1] = their scan (koff[nr]: the lanes the kill takes) ...
+hipError_t launch_rs_kill_scan(const RetainWork& w, uint32_t nr, uint32_t* len, uint64_t* koff, hipStream_t s);
+// ... and every covered rank of msg[m] that is not a tombstone yet becomes one; out[m] gets its
+// {rank, message id} once, *n_out = how many
+hipError_t launch_rs_kill(const RetainWork& w, uint32_t nr, const uint64_t* koff, uint64_t total, uint32_t m,
+                          uint32_t* msg, uint2* out, uint32_t* n_out, hipStream_t s);
 
 }  // namespace egm

@@ -3101,6 +3101,59 @@ __global__ __launch_bounds__(256) void k_rs_expire(const uint64_t* __restrict__ 
   }
 }
 
+// delete_message/2 with filters (emqx_retainer_mnesia.erl:114-116, 206-212)
+// over the image: the walk's emitted ranges, run with now = 0, cover every
+// rank a filter of the batch matches.  k_rs_range_len gives each range its
+// rank count (RS_SINGLE: one), the scan of the counts numbers the ranks of
+// the whole list, and k_rs_kill takes one lane per rank: its range by binary
+// search over the scan, as k_rs_fill, so a '#' range of a million ranks is
+// spread over the grid like any other.  The exchange is the dedup: of the
+// lanes that reach one rank (a/# and a/+ in one batch) exactly one reads a
+// message id back, the others and a rank deleted earlier read RS_TOMB.  The
+// {rank, id} pairs are appended wave-aggregated, as rs_emit; out holds one
+// pair per image rank, and each rank is appended once at most.
+__global__ __launch_bounds__(256) void k_rs_range_len(const uint32_t* __restrict__ rlo,
+                                                      const uint32_t* __restrict__ rhi, uint32_t nr,
+                                                      uint32_t* __restrict__ len) {
+  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < nr; r += gridDim.x * blockDim.x) {
+    const uint32_t hi = rhi[r];
+    len[r] = (hi & RS_SINGLE) ? 1u : hi - rlo[r];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_rs_kill(const uint32_t* __restrict__ rlo, const uint64_t* __restrict__ koff,
+                                                 uint32_t nr, uint64_t total, uint32_t m, uint32_t* __restrict__ msg,
+                                                 uint2* __restrict__ out, uint32_t* __restrict__ n_out) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  const uint64_t n_iter = (total + stride - 1) / stride;   // uniform trip count: the wave ballots
+  for (uint64_t it = 0; it < n_iter; ++it) {
+    const uint64_t q = it * stride + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool on = false;
+    uint32_t rank = 0, old = RS_TOMB;
+    if (q < total) {
+      uint32_t lo = 0, hi = nr;            // largest range with koff[range] <= q
+      while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (koff[mid] <= q) lo = mid;
+        else hi = mid;
+      }
+      rank = rlo[lo] + (uint32_t)(q - koff[lo]);
+      if (rank < m) {                      // always, for ranges of this image
+        old = atomicExch(&msg[rank], RS_TOMB);
+        on = old != RS_TOMB;
+      }
+    }
+    const uint64_t b = __ballot(on);
+    if (!b) continue;
+    const uint32_t leader = __builtin_ctzll(b);
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(n_out, (uint32_t)__popcll(b));
+    base = __shfl(base, leader, 64);
+    if (on) out[base + (uint32_t)__popcll(b & ((1ull << lane) - 1))] = uint2{rank, old};
+  }
+}
+
 hipError_t launch_tokenise(const DevTable& tab, const uint8_t* blob, uint64_t nbytes, const uint32_t* off, uint32_t n,
                            uint32_t* wid, uint32_t* lv, uint8_t* tfl, hipStream_t s) {
   const WalkOrderOut none{};
@@ -3166,6 +3219,29 @@ hipError_t launch_rs_expire(const uint64_t* expiry, uint32_t* msg, uint32_t m, u
   hipError_t e = hipMemsetAsync(n_out, 0, 4, s);
   if (e != hipSuccess) return e;
   if (m) hipLaunchKernelGGL(k_rs_expire, dim3(grid_for(m)), dim3(256), 0, s, expiry, msg, m, now, out, n_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_rs_ov_masks(const RetainWork& w, const RetainOverlay& o, const uint8_t* fblob, uint32_t n,
+                              hipStream_t s) {
+  hipError_t e = hipMemsetAsync(w.fcnt, 0, ((size_t)n + 1) * 4, s);
+  if (e != hipSuccess) return e;
+  if (o.n && n) hipLaunchKernelGGL(k_rs_ov_count, dim3(ov_grid(o, n)), dim3(256), 0, s, o, w, fblob, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_rs_kill_scan(const RetainWork& w, uint32_t nr, uint32_t* len, uint64_t* koff, hipStream_t s) {
+  if (nr) hipLaunchKernelGGL(k_rs_range_len, dim3(grid_for(nr)), dim3(256), 0, s, w.rlo, w.rhi, nr, len);
+  scan_counts(len, nr, w.tiles, koff, s);
+  return hipGetLastError();
+}
+
+hipError_t launch_rs_kill(const RetainWork& w, uint32_t nr, const uint64_t* koff, uint64_t total, uint32_t m,
+                          uint32_t* msg, uint2* out, uint32_t* n_out, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(n_out, 0, 4, s);
+  if (e != hipSuccess) return e;
+  if (nr && total)
+    hipLaunchKernelGGL(k_rs_kill, dim3(grid_for(total)), dim3(256), 0, s, w.rlo, koff, nr, total, m, msg, out, n_out);
   return hipGetLastError();
 }
 

@@ -2,9 +2,11 @@
 // (C-ABI in include/emqx_gpu_match.h, egm_rstore_*).
 //
 // Mirrors apps/emqx_retainer/src/emqx_retainer_mnesia.erl:
-//   store_retained/2 :73-101  -> egm_rstore_put     (a topic keeps one record)
-//   delete_message/2 :114-129 -> egm_rstore_delete  (plain topic; a wildcard
-//                                delete is match + delete, see retainer.py)
+//   store_retained/2 :73-101  -> egm_rstore_put     (a topic keeps one record;
+//                                is_table_full/0 :230-240 as egm_rstore_set_max_retained)
+//   delete_message/2 :114-129 -> egm_rstore_delete  (plain topic) and, with
+//                                match_delete_messages/1 :206-212,
+//                                egm_rstore_delete_matching (filters)
 //   clean/1          :148-150 -> egm_rstore_clean
 //   clear_expired/1  :103-112 -> egm_rstore_clear_expired
 //   match_messages/1 :200-204 -> egm_rstore_match   (condition/1 :215-220,
@@ -241,6 +243,7 @@ struct egm_rstore {
   std::vector<uint32_t> touched; // image ranks to patch
   uint64_t dead_ranks = 0;       // tombstones on the device
   uint32_t ov_cap = 4096;
+  uint64_t max_retained = 0;     // max_retained_messages (:230-240); 0: no limit
   bool reset = true;             // the image is to be dropped (a new store, clean)
   bool ov_dirty = false;         // the device overlay is out of date
   struct {
@@ -436,6 +439,119 @@ static bool has_wildcard_word(const uint8_t* p, uint32_t len) {
   return false;
 }
 
+// a batch of filters as blob + offsets[n + 1], the argument form of the match and of the delete
+static bool rs_filters_ok(const uint8_t* blob, const uint32_t* off, uint32_t n) {
+  if (n && !off) return false;
+  for (uint32_t i = 0; i < n; ++i)
+    if (off[i + 1] < off[i]) return false;
+  return !(n && !blob && off[n] > off[0]);
+}
+
+// The frontier walk of a batch of filters over the committed image, shared by
+// egm_rstore_match and egm_rstore_delete_matching: the filters go to the
+// device (in_blob, in_off) and are tokenised, then k_rs_init and one k_rs_step /
+// scan / k_rs_fill round per level; a range list that overflows is walked again
+// with room.  On return *w describes the batch, w->rf/rlo/rhi hold *n_ranges
+// ranges, w->fcnt[n + 1] is allocated and the stream is synchronised.
+// with_alive: also the alive flags at `now` and their scan (w->alive, w->apre),
+// which the match's rows count from.
+static int rs_walk(egm_rstore* r, const uint8_t* blob, const uint32_t* off, uint32_t n, uint64_t now, bool ge_plain,
+                   bool with_alive, RetainWork* wp, uint32_t* n_ranges_out) {
+  RetainWork& w = *wp;
+  hipStream_t s = r->stream;
+  hipError_t e;
+  const uint32_t base0 = n ? off[0] : 0;
+  const uint64_t bytes = n ? (uint64_t)off[n] - base0 : 0;
+  std::vector<uint32_t> loff(n + 1);
+  for (uint32_t i = 0; i <= n; ++i) loff[i] = n ? off[i] - base0 : 0;
+  const uint32_t M = r->view.n_topics;
+  const size_t nn = (size_t)n + 1;
+  if ((e = r->in_blob.ensure(bytes + 16)) || (e = r->in_off.ensure(nn * 4)) ||
+      (e = r->wid.ensure((bytes + nn) * 4)) || (e = r->lv.ensure(nn * 4)) || (e = r->tfl.ensure(nn)) ||
+      (with_alive && ((e = r->alive.ensure(((size_t)M + 1) * 4)) || (e = r->apre.ensure(((size_t)M + 2) * 8)))) ||
+      (e = r->fcnt.ensure(nn * 4)) || (e = r->nr.ensure(16)))
+    return r->hip_fail(e, "retained workspace");
+  if (bytes && (e = hipMemcpyAsync(r->in_blob.p, blob + base0, bytes, hipMemcpyHostToDevice, s)))
+    return r->hip_fail(e, "H2D filters");
+  if ((e = hipMemcpyAsync(r->in_off.p, loff.data(), nn * 4, hipMemcpyHostToDevice, s)))
+    return r->hip_fail(e, "H2D offsets");
+
+  w.off = r->in_off.as<uint32_t>();
+  w.wid = r->wid.as<uint32_t>();
+  w.lv = r->lv.as<uint32_t>();
+  w.tfl = r->tfl.as<uint8_t>();
+  w.alive = with_alive ? r->alive.as<uint32_t>() : nullptr;
+  w.apre = with_alive ? r->apre.as<uint64_t>() : nullptr;
+  w.fcnt = r->fcnt.as<uint32_t>();
+  w.n_ranges = r->nr.as<uint32_t>();
+  w.now = now;
+  w.ge_plain = ge_plain;
+  auto tiles_for = [&](uint64_t m) { return (scan_tiles((uint32_t)std::min<uint64_t>(m, 0xFFFFFFFFull)) + 2) * 8; };
+  size_t tiles_need = std::max(tiles_for(with_alive ? M : 0), tiles_for(n));
+  if ((e = r->tiles.ensure(tiles_need))) return r->hip_fail(e, "tiles");
+  w.tiles = r->tiles.as<uint64_t>();
+
+  if ((e = launch_tokenise(r->dtab, r->in_blob.as<uint8_t>(), bytes, w.off, n, r->wid.as<uint32_t>(), r->lv.as<uint32_t>(),
+                           r->tfl.as<uint8_t>(), s)) ||
+      (with_alive && (e = launch_rs_alive(r->view, w, s))))
+    return r->hip_fail(e, "tokenise/alive");
+
+  // frontier walk, level by level; ranges may overflow -> rerun with room
+  uint64_t range_cap = std::max<uint64_t>(4 * (uint64_t)n + 1024, r->rf.cap / 4);
+  uint32_t n_ranges = 0;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    if (range_cap > 0xFFFFFFF0ull) return r->fail(EGM_E_NOMEM, "too many result ranges in one batch");
+    if ((e = r->rf.ensure(range_cap * 4)) || (e = r->rlo.ensure(range_cap * 4)) || (e = r->rhi.ensure(range_cap * 4)) ||
+        (e = r->roff.ensure(range_cap * 4)))
+      return r->hip_fail(e, "ranges");
+    w.rf = r->rf.as<uint32_t>();
+    w.rlo = r->rlo.as<uint32_t>();
+    w.rhi = r->rhi.as<uint32_t>();
+    w.roff = r->roff.as<uint32_t>();
+    w.range_cap = (uint32_t)range_cap;
+    if ((e = hipMemsetAsync(w.n_ranges, 0, 4, s))) return r->hip_fail(e, "memset");
+    uint64_t np = n;
+    int cur = 0;
+    if ((e = r->pf[0].ensure(nn * 4)) || (e = r->pn[0].ensure(nn * 4))) return r->hip_fail(e, "frontier");
+    if ((e = launch_rs_init(n, r->pf[0].as<uint32_t>(), r->pn[0].as<uint32_t>(), s)))
+      return r->hip_fail(e, "init");
+    for (uint32_t level = 0; np; ++level) {
+      if (np > 0xFFFFFFF0ull) return r->fail(EGM_E_NOMEM, "frontier too large (split the batch)");
+      if ((e = r->pc.ensure((np + 1) * 4)) || (e = r->paux.ensure((np + 1) * 4)) ||
+          (e = r->poff.ensure((np + 2) * 8)) || (e = r->tiles.ensure(std::max(tiles_need, tiles_for(np)))))
+        return r->hip_fail(e, "level workspace");
+      w.pc = r->pc.as<uint32_t>();
+      w.paux = r->paux.as<uint32_t>();
+      w.poff = r->poff.as<uint64_t>();
+      w.tiles = r->tiles.as<uint64_t>();
+      if ((e = launch_rs_level(r->view, w, level, (uint32_t)np, r->pf[cur].as<uint32_t>(), r->pn[cur].as<uint32_t>(),
+                               s)))
+        return r->hip_fail(e, "level");
+      uint64_t nnext = 0;
+      if ((e = hipMemcpyAsync(&nnext, w.poff + np, 8, hipMemcpyDeviceToHost, s)) || (e = hipStreamSynchronize(s)))
+        return r->hip_fail(e, "level readback");
+      if (nnext) {
+        if ((e = r->pf[cur ^ 1].ensure(nnext * 4 + 16)) || (e = r->pn[cur ^ 1].ensure(nnext * 4 + 16)))
+          return r->hip_fail(e, "frontier");
+        if ((e = launch_rs_fill(w, (uint32_t)np, nnext, r->pf[cur].as<uint32_t>(), r->pf[cur ^ 1].as<uint32_t>(),
+                                r->pn[cur ^ 1].as<uint32_t>(), s)))
+          return r->hip_fail(e, "fill");
+        // the next level may grow (reallocate) the buffers this fill reads
+        if ((e = hipStreamSynchronize(s))) return r->hip_fail(e, "fill sync");
+      }
+      cur ^= 1;
+      np = nnext;
+    }
+    if ((e = hipMemcpyAsync(&n_ranges, w.n_ranges, 4, hipMemcpyDeviceToHost, s)) || (e = hipStreamSynchronize(s)))
+      return r->hip_fail(e, "ranges readback");
+    if (n_ranges <= range_cap) break;
+    range_cap = (uint64_t)n_ranges + n_ranges / 4 + 1024;
+    if (attempt == 1) return r->fail(EGM_E_NOMEM, "ranges capacity");
+  }
+  *n_ranges_out = n_ranges;
+  return EGM_OK;
+}
+
 extern "C" {
 
 int egm_rstore_open(int device, egm_rstore** out) {
@@ -474,7 +590,12 @@ int egm_rstore_put(egm_rstore* r, const uint8_t* topic, uint32_t len, uint32_t m
   if (msg_id == RS_TOMB) return EGM_E_INVAL;               // the image's tombstone mark
   if (has_wildcard_word(topic, len)) return EGM_E_INVAL;   // publish topics carry no wildcard
   std::lock_guard<std::mutex> g(r->mu);
-  auto [it, fresh] = r->recs.try_emplace(std::string((const char*)topic, len));
+  std::string key((const char*)topic, len);
+  if (r->max_retained && r->n_live >= r->max_retained) {   // is_table_full/0: only a held topic is written (:82-98)
+    auto held = r->recs.find(key);
+    if (held == r->recs.end() || held->second.dead) return r->fail(EGM_E_FULL, "the retained table is full");
+  }
+  auto [it, fresh] = r->recs.try_emplace(std::move(key));
   Rec& x = it->second;
   if (fresh) {                       // not in the image: the overlay
     x.ov = (uint32_t)r->ov_ents.size();
@@ -548,6 +669,13 @@ int egm_rstore_set_overlay_cap(egm_rstore* r, uint32_t max_topics) {
   return EGM_OK;
 }
 
+int egm_rstore_set_max_retained(egm_rstore* r, uint64_t max) {
+  if (!r) return EGM_E_INVAL;
+  std::lock_guard<std::mutex> g(r->mu);
+  r->max_retained = max;
+  return EGM_OK;
+}
+
 int egm_rstore_last_commit(egm_rstore* r, int* rebuilt, uint64_t* patched, uint64_t* tombstoned,
                            uint64_t* overlay_topics, uint64_t* dead_ranks, uint64_t* h2d_bytes) {
   if (!r || !rebuilt || !patched || !tombstoned || !overlay_topics || !dead_ranks || !h2d_bytes) return EGM_E_INVAL;
@@ -608,13 +736,95 @@ int egm_rstore_clear_expired(egm_rstore* r, uint64_t now_ms, uint32_t** msg_ids,
   return EGM_OK;
 }
 
+int egm_rstore_delete_matching(egm_rstore* r, const uint8_t* blob, const uint32_t* off, uint32_t n, uint32_t** msg_ids,
+                               uint64_t* n_ids) {
+  if (!r || !msg_ids || !n_ids) return EGM_E_INVAL;
+  if (!rs_filters_ok(blob, off, n)) return EGM_E_INVAL;
+  *msg_ids = nullptr;
+  *n_ids = 0;
+  std::lock_guard<std::mutex> g(r->mu);
+  if (hipSetDevice(r->device) != hipSuccess) return EGM_E_DEVICE;
+  int rc = rs_commit_locked(r);   // the device's image, tombstones and overlay are the records'
+  if (rc) return rc;
+  if (!n || !r->n_live) return EGM_OK;
+  hipStream_t s = r->stream;
+  hipError_t e;
+  // now = 0: rs_alive holds for every expiry, so the walk emits every rank a
+  // filter matches, expired or not (:209-211); no alive scan is needed
+  RetainWork w{};
+  uint32_t nr = 0;
+  if ((rc = rs_walk(r, blob, off, n, 0, false, false, &w, &nr))) return rc;
+
+  // the image: one exchange per covered rank
+  const uint32_t M = r->view.n_topics;
+  uint32_t k = 0;
+  std::vector<uint2> killed;
+  if (nr) {
+    uint64_t total = 0;
+    if ((e = r->pc.ensure(((size_t)nr + 1) * 4)) || (e = r->poff.ensure(((size_t)nr + 2) * 8)) ||
+        (e = r->tiles.ensure((scan_tiles(nr) + 2) * 8)) || (e = r->xout.ensure((size_t)M * 8 + 16)) ||
+        (e = r->xn.ensure(16)))
+      return r->hip_fail(e, "kill workspace");
+    w.tiles = r->tiles.as<uint64_t>();
+    uint64_t* koff = r->poff.as<uint64_t>();
+    if ((e = launch_rs_kill_scan(w, nr, r->pc.as<uint32_t>(), koff, s)) ||
+        (e = hipMemcpyAsync(&total, koff + nr, 8, hipMemcpyDeviceToHost, s)) || (e = hipStreamSynchronize(s)))
+      return r->hip_fail(e, "kill scan");
+    if ((e = launch_rs_kill(w, nr, koff, total, M, r->msg.as<uint32_t>(), r->xout.as<uint2>(), r->xn.as<uint32_t>(),
+                            s)) ||
+        (e = hipMemcpyAsync(&k, r->xn.p, 4, hipMemcpyDeviceToHost, s)) || (e = hipStreamSynchronize(s)))
+      return r->hip_fail(e, "kill");
+    killed.resize(k);
+    if (k && ((e = hipMemcpyAsync(killed.data(), r->xout.p, (size_t)k * 8, hipMemcpyDeviceToHost, s)) ||
+              (e = hipStreamSynchronize(s))))
+      return r->hip_fail(e, "kill readback");
+  }
+  std::vector<uint32_t> gone;
+  gone.reserve(k);
+  for (const uint2& kr : killed) {   // {rank, the id it held}: the kernel made these ranks tombstones
+    Rec& x = r->by_rank[kr.x]->second;
+    gone.push_back(kr.y);
+    x.dead = x.dev_dead = true;
+  }
+  r->dead_ranks += k;
+
+  // the overlay: the byte match's masks, OR-ed per tile over the batch
+  RetainOverlay ov = r->ov;
+  const uint32_t ov_tiles = (ov.n + 63) / 64;
+  if (ov_tiles) {
+    const uint64_t ov_pairs = (uint64_t)n * ov_tiles;
+    if ((e = r->ovmask.ensure(ov_pairs * 8 + 16)) || (e = r->ovbase.ensure(ov_pairs * 4 + 16)))
+      return r->hip_fail(e, "overlay workspace");
+    ov.mask = r->ovmask.as<uint64_t>();
+    ov.base = r->ovbase.as<uint32_t>();
+    std::vector<uint64_t> masks(ov_pairs), hit(ov_tiles, 0);
+    if ((e = launch_rs_ov_masks(w, ov, r->in_blob.as<uint8_t>(), n, s)) ||
+        (e = hipMemcpyAsync(masks.data(), ov.mask, ov_pairs * 8, hipMemcpyDeviceToHost, s)) ||
+        (e = hipStreamSynchronize(s)))
+      return r->hip_fail(e, "overlay masks");
+    for (uint64_t q = 0; q < ov_pairs; ++q) hit[q % ov_tiles] |= masks[q];
+    for (size_t p = r->ov_ents.size(); p-- > 0;) {   // downwards: ov_remove moves the last entry into the hole
+      if (!((hit[p >> 6] >> (p & 63)) & 1)) continue;
+      Ent* en = r->ov_ents[p];
+      gone.push_back(en->second.msg);
+      r->ov_remove(en->second);
+      r->recs.erase(r->recs.find(en->first));
+    }
+  }
+  r->n_live -= gone.size();
+  if (gone.empty()) return EGM_OK;
+  uint32_t* mem = (uint32_t*)result_alloc(gone.size() * 4);
+  if (!mem) return r->fail(EGM_E_NOMEM, "result");
+  memcpy(mem, gone.data(), gone.size() * 4);
+  *msg_ids = mem;
+  *n_ids = gone.size();
+  return EGM_OK;
+}
+
 int egm_rstore_match(egm_rstore* r, const uint8_t* blob, const uint32_t* off, uint32_t n, uint64_t now_ms, int mode,
                      egm_result** out) {
   if (!r || !out || (mode != EGM_RMODE_MATCH && mode != EGM_RMODE_DISPATCH)) return EGM_E_INVAL;
-  if (n && !off) return EGM_E_INVAL;
-  for (uint32_t i = 0; i < n; ++i)
-    if (off[i + 1] < off[i]) return EGM_E_INVAL;
-  if (n && !blob && off[n] > off[0]) return EGM_E_INVAL;
+  if (!rs_filters_ok(blob, off, n)) return EGM_E_INVAL;
   *out = nullptr;
   std::lock_guard<std::mutex> g(r->mu);
   if (hipSetDevice(r->device) != hipSuccess) return EGM_E_DEVICE;
@@ -622,95 +832,11 @@ int egm_rstore_match(egm_rstore* r, const uint8_t* blob, const uint32_t* off, ui
   if (rc) return rc;
   hipStream_t s = r->stream;
   hipError_t e;
-  const uint32_t base0 = n ? off[0] : 0;
-  const uint64_t bytes = n ? (uint64_t)off[n] - base0 : 0;
-  std::vector<uint32_t> loff(n + 1);
-  for (uint32_t i = 0; i <= n; ++i) loff[i] = n ? off[i] - base0 : 0;
-  const uint32_t M = r->view.n_topics;
   const size_t nn = (size_t)n + 1;
-  if ((e = r->in_blob.ensure(bytes + 16)) || (e = r->in_off.ensure(nn * 4)) ||
-      (e = r->wid.ensure((bytes + nn) * 4)) || (e = r->lv.ensure(nn * 4)) || (e = r->tfl.ensure(nn)) ||
-      (e = r->alive.ensure(((size_t)M + 1) * 4)) || (e = r->apre.ensure(((size_t)M + 2) * 8)) ||
-      (e = r->fcnt.ensure(nn * 4)) || (e = r->row.ensure(nn * 8)) || (e = r->nr.ensure(16)))
-    return r->hip_fail(e, "retained workspace");
-  if (bytes && (e = hipMemcpyAsync(r->in_blob.p, blob + base0, bytes, hipMemcpyHostToDevice, s)))
-    return r->hip_fail(e, "H2D filters");
-  if ((e = hipMemcpyAsync(r->in_off.p, loff.data(), nn * 4, hipMemcpyHostToDevice, s)))
-    return r->hip_fail(e, "H2D offsets");
-
+  if ((e = r->row.ensure(nn * 8))) return r->hip_fail(e, "retained workspace");
   RetainWork w{};
-  w.off = r->in_off.as<uint32_t>();
-  w.wid = r->wid.as<uint32_t>();
-  w.lv = r->lv.as<uint32_t>();
-  w.tfl = r->tfl.as<uint8_t>();
-  w.alive = r->alive.as<uint32_t>();
-  w.apre = r->apre.as<uint64_t>();
-  w.fcnt = r->fcnt.as<uint32_t>();
-  w.n_ranges = r->nr.as<uint32_t>();
-  w.now = now_ms;
-  w.ge_plain = mode == EGM_RMODE_DISPATCH;
-  auto tiles_for = [&](uint64_t m) { return (scan_tiles((uint32_t)std::min<uint64_t>(m, 0xFFFFFFFFull)) + 2) * 8; };
-  size_t tiles_need = std::max(tiles_for(M), tiles_for(n));
-  if ((e = r->tiles.ensure(tiles_need))) return r->hip_fail(e, "tiles");
-  w.tiles = r->tiles.as<uint64_t>();
-
-  if ((e = launch_tokenise(r->dtab, r->in_blob.as<uint8_t>(), bytes, w.off, n, r->wid.as<uint32_t>(), r->lv.as<uint32_t>(),
-                           r->tfl.as<uint8_t>(), s)) ||
-      (e = launch_rs_alive(r->view, w, s)))
-    return r->hip_fail(e, "tokenise/alive");
-
-  // frontier walk, level by level; ranges may overflow -> rerun with room
-  uint64_t range_cap = std::max<uint64_t>(4 * (uint64_t)n + 1024, r->rf.cap / 4);
   uint32_t n_ranges = 0;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    if (range_cap > 0xFFFFFFF0ull) return r->fail(EGM_E_NOMEM, "too many result ranges in one batch");
-    if ((e = r->rf.ensure(range_cap * 4)) || (e = r->rlo.ensure(range_cap * 4)) || (e = r->rhi.ensure(range_cap * 4)) ||
-        (e = r->roff.ensure(range_cap * 4)))
-      return r->hip_fail(e, "ranges");
-    w.rf = r->rf.as<uint32_t>();
-    w.rlo = r->rlo.as<uint32_t>();
-    w.rhi = r->rhi.as<uint32_t>();
-    w.roff = r->roff.as<uint32_t>();
-    w.range_cap = (uint32_t)range_cap;
-    if ((e = hipMemsetAsync(w.n_ranges, 0, 4, s))) return r->hip_fail(e, "memset");
-    uint64_t np = n;
-    int cur = 0;
-    if ((e = r->pf[0].ensure(nn * 4)) || (e = r->pn[0].ensure(nn * 4))) return r->hip_fail(e, "frontier");
-    if ((e = launch_rs_init(n, r->pf[0].as<uint32_t>(), r->pn[0].as<uint32_t>(), s)))
-      return r->hip_fail(e, "init");
-    for (uint32_t level = 0; np; ++level) {
-      if (np > 0xFFFFFFF0ull) return r->fail(EGM_E_NOMEM, "frontier too large (split the batch)");
-      if ((e = r->pc.ensure((np + 1) * 4)) || (e = r->paux.ensure((np + 1) * 4)) ||
-          (e = r->poff.ensure((np + 2) * 8)) || (e = r->tiles.ensure(std::max(tiles_need, tiles_for(np)))))
-        return r->hip_fail(e, "level workspace");
-      w.pc = r->pc.as<uint32_t>();
-      w.paux = r->paux.as<uint32_t>();
-      w.poff = r->poff.as<uint64_t>();
-      w.tiles = r->tiles.as<uint64_t>();
-      if ((e = launch_rs_level(r->view, w, level, (uint32_t)np, r->pf[cur].as<uint32_t>(), r->pn[cur].as<uint32_t>(),
-                               s)))
-        return r->hip_fail(e, "level");
-      uint64_t nnext = 0;
-      if ((e = hipMemcpyAsync(&nnext, w.poff + np, 8, hipMemcpyDeviceToHost, s)) || (e = hipStreamSynchronize(s)))
-        return r->hip_fail(e, "level readback");
-      if (nnext) {
-        if ((e = r->pf[cur ^ 1].ensure(nnext * 4 + 16)) || (e = r->pn[cur ^ 1].ensure(nnext * 4 + 16)))
-          return r->hip_fail(e, "frontier");
-        if ((e = launch_rs_fill(w, (uint32_t)np, nnext, r->pf[cur].as<uint32_t>(), r->pf[cur ^ 1].as<uint32_t>(),
-                                r->pn[cur ^ 1].as<uint32_t>(), s)))
-          return r->hip_fail(e, "fill");
-        // the next level may grow (reallocate) the buffers this fill reads
-        if ((e = hipStreamSynchronize(s))) return r->hip_fail(e, "fill sync");
-      }
-      cur ^= 1;
-      np = nnext;
-    }
-    if ((e = hipMemcpyAsync(&n_ranges, w.n_ranges, 4, hipMemcpyDeviceToHost, s)) || (e = hipStreamSynchronize(s)))
-      return r->hip_fail(e, "ranges readback");
-    if (n_ranges <= range_cap) break;
-    range_cap = (uint64_t)n_ranges + n_ranges / 4 + 1024;
-    if (attempt == 1) return r->fail(EGM_E_NOMEM, "ranges capacity");
-  }
+  if ((rc = rs_walk(r, blob, off, n, now_ms, mode == EGM_RMODE_DISPATCH, true, &w, &n_ranges))) return rc;
   uint64_t* d_row = r->row.as<uint64_t>();
   RetainOverlay ov = r->ov;   // one mask and base per (filter, tile of 64 overlay topics)
   const uint64_t ov_pairs = (uint64_t)n * ((ov.n + 63) / 64);

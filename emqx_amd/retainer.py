@@ -11,7 +11,9 @@ the C-ABI library (``egm_rstore_*``): a word trie of the stored topics in HBM,
 walked level by level for a whole batch of filters at once.  Messages stay on
 the host; the device holds topic -> message-id records.  Puts and deletes are
 applied incrementally (patches, tombstones, an overlay of new topics; DESIGN
-§4.3), and ``clear_expired/1`` (:103-112) runs on the device.
+§4.3), and ``clear_expired/1`` (:103-112) and a wildcard ``delete_message/2``
+(:114-116, 206-212) run on the device.  ``max_retained_messages``
+(``is_table_full/0`` :230-240) is the store's size limit.
 """
 from __future__ import annotations
 
@@ -56,26 +58,55 @@ class RetainedStore:
             raise L.EgmError(rc, f"{what}: {msg.decode() if msg else ''}")
 
     # -- records ---------------------------------------------------------------
-    def store_retained(self, topic: bytes, msg=None, expiry_time: int = 0, timestamp: int = 0):
-        """``store_retained/2`` (:73-101): the topic's record is replaced."""
+    def store_retained(self, topic: bytes, msg=None, expiry_time: int = 0, timestamp: int = 0) -> bool:
+        """``store_retained/2`` (:73-101): the topic's record is replaced.
+        ``False`` when the table is full and the topic is a new one (:92-97;
+        the reference logs an error and answers ``ok``); nothing is stored then."""
+        mid = self._next
+        self._next += 1
+        rc = self.lib.egm_rstore_put(self.h, topic, len(topic), mid, expiry_time)
+        if rc == L.EGM_E_FULL:
+            return False
+        self._check(rc, "egm_rstore_put")
         old = self._by_topic.get(topic)
         if old is not None:
             del self._msgs[old]
-        mid = self._next
-        self._next += 1
-        self._check(self.lib.egm_rstore_put(self.h, topic, len(topic), mid, expiry_time), "egm_rstore_put")
         self._msgs[mid] = (topic, topic if msg is None else msg, timestamp)
         self._by_topic[topic] = mid
+        return True
+
+    def set_max_retained(self, n: int):
+        """``max_retained_messages`` (``is_table_full/0`` :230-240): with ``n``
+        topics held, only a held topic can be stored again; 0 lifts the limit."""
+        self._check(self.lib.egm_rstore_set_max_retained(self.h, n), "egm_rstore_set_max_retained")
 
     def delete_message(self, topic: bytes):
         """``delete_message/2`` (:114-129): a wildcard filter deletes every
         record its pattern matches, expired or not (``match_delete_messages``
         :206-212)."""
         if wildcard(topic):
-            for mid in self.match_ids([topic], now=0, mode=L.EGM_RMODE_MATCH)[0]:
-                self._drop(self._msgs[int(mid)][0])
+            self.delete_matching([topic])
         else:
             self._drop(topic)
+
+    def delete_matching(self, filters: Sequence[bytes]) -> List[int]:
+        """``delete_message/2`` for a batch of filters in one device call: every
+        record a filter's pattern matches goes, expired or not; a filter
+        without wildcards deletes its own topic.  Returns the dropped ids."""
+        blob, off = pack_strings(list(filters))
+        ids = L._u32p()
+        n = C.c_uint64()
+        self._check(self.lib.egm_rstore_delete_matching(self.h, C.c_void_p(blob.ctypes.data),
+                                                        C.c_void_p(off.ctypes.data), len(filters), C.byref(ids),
+                                                        C.byref(n)), "egm_rstore_delete_matching")
+        try:
+            gone = np.ctypeslib.as_array(ids, shape=(n.value,)).tolist() if n.value else []
+        finally:
+            self.lib.egm_result_free(ids)
+        for mid in gone:
+            topic = self._msgs.pop(mid)[0]
+            del self._by_topic[topic]
+        return gone
 
     def _drop(self, topic: bytes):
         mid = self._by_topic.pop(topic, None)

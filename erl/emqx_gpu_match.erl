@@ -19,6 +19,9 @@
 
 -export([open/1, build/2, apply_delta/3, match_batch/3, submit/3, wait/2, cancel/2, subs_build/2,
          subs_delta/3, publish_batch/2]).
+%% the retained store (emqx_retainer_mnesia's table mirrored on the device)
+-export([rs_open/1, rs_put/4, rs_delete/2, rs_delete_matching/2, rs_set_max_retained/2, rs_clean/1, rs_size/1, rs_commit/1,
+         rs_clear_expired/2, rs_match/4]).
 -export([init/0, ctx/0, filter_of/1, filters_of/1, build/1, sync/2, match/1, match_routes/1]).
 
 -on_load(load_nif/0).
@@ -45,6 +48,20 @@ cancel(_Ctx, _Ticket) -> erlang:nif_error(nif_not_loaded).
 subs_build(_Ctx, _SubsByFilterId) -> erlang:nif_error(nif_not_loaded).
 subs_delta(_Ctx, _Adds, _Dels) -> erlang:nif_error(nif_not_loaded).
 publish_batch(_Ctx, _Topics) -> erlang:nif_error(nif_not_loaded).
+%% Retained store: topic -> {MsgId, ExpiryMs}; the messages stay with the caller.
+%% rs_put/4 -> ok | {error, full}; rs_delete_matching/2 and rs_clear_expired/2
+%% -> {ok, [MsgId]} (the dropped ids); rs_match/4 -> {ok, [[MsgId]]} per filter,
+%% Mode 0 = match_messages/1, 1 = dispatch/4 (plain topics by read_messages/1).
+rs_open(_Device) -> erlang:nif_error(nif_not_loaded).
+rs_put(_Store, _Topic, _MsgId, _ExpiryMs) -> erlang:nif_error(nif_not_loaded).
+rs_delete(_Store, _Topic) -> erlang:nif_error(nif_not_loaded).
+rs_delete_matching(_Store, _Filters) -> erlang:nif_error(nif_not_loaded).
+rs_set_max_retained(_Store, _Max) -> erlang:nif_error(nif_not_loaded).
+rs_clean(_Store) -> erlang:nif_error(nif_not_loaded).
+rs_size(_Store) -> erlang:nif_error(nif_not_loaded).
+rs_commit(_Store) -> erlang:nif_error(nif_not_loaded).
+rs_clear_expired(_Store, _NowMs) -> erlang:nif_error(nif_not_loaded).
+rs_match(_Store, _Filters, _NowMs, _Mode) -> erlang:nif_error(nif_not_loaded).
 
 %% ---------------------------------------------------------------------
 %% emqx_trie-shaped API

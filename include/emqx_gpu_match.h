@@ -50,6 +50,7 @@ extern "C" {
 #define EGM_E_OVERFLOW (-4)  /* a topic's frontier exceeded the heavy-path stack */
 #define EGM_E_STATE (-5)     /* call not valid in the current state */
 #define EGM_E_NOTFOUND (-6)  /* unknown filter id */
+#define EGM_E_FULL (-7)      /* the retained store is at its size limit (egm_rstore_set_max_retained) */
 
 /* Match semantics. */
 #define EGM_MODE_TRIE 0   /* emqx_trie:match/1 over the table's filters            */
@@ -408,8 +409,11 @@ void egm_result_free(void* result);
      egm_rstore_put     <- store_retained/2  :73-101 (one record per topic;
                            topics with a '+'/'#' word are rejected: EGM_E_INVAL,
                            and so is the message id 0xFFFFFFFF, which marks a
-                           deleted topic inside the device image)
+                           deleted topic inside the device image); with a size
+                           limit set, is_table_full/0 :75-99, 230-240
      egm_rstore_delete  <- delete_message/2  :114-129 (plain topic)
+     egm_rstore_delete_matching <- delete_message/2 :114-129 with
+                           match_delete_messages/1 :206-212 (wildcard filters)
      egm_rstore_clean   <- clean/1           :148-150
      egm_rstore_clear_expired <- clear_expired/1 :103-112 (the timer of
                            apps/emqx_retainer/src/emqx_retainer.erl:209-213):
@@ -463,6 +467,21 @@ int egm_rstore_last_commit(egm_rstore* rs, int* rebuilt, uint64_t* patched, uint
    returns their message ids: *msg_ids (NULL when *n == 0) is freed with
    egm_result_free. */
 int egm_rstore_clear_expired(egm_rstore* rs, uint64_t now_ms, uint32_t** msg_ids, uint64_t* n);
+/* delete_message/2 for a batch of filters (emqx_retainer_mnesia.erl:114-129,
+   206-212): every stored topic that condition/1 of a filter matches is
+   deleted, expired or not; a filter without wildcards deletes its own topic.
+   One device call: the filters walk the image as in egm_rstore_match and every
+   rank they cover becomes a tombstone; the overlay is matched on its bytes.
+   Returns the dropped message ids (each once, unordered; *msg_ids is NULL
+   when *n_ids == 0); free with egm_result_free. */
+int egm_rstore_delete_matching(egm_rstore* rs, const uint8_t* filters_blob, const uint32_t* offsets,
+                               uint32_t n, uint32_t** msg_ids, uint64_t* n_ids);
+/* max_retained_messages (is_table_full/0, :230-240); 0 (the default) = no
+   limit.  With a limit, egm_rstore_put of a topic the store does not hold
+   returns EGM_E_FULL and stores nothing while egm_rstore_size >= max (:92-97);
+   a put on a held topic always succeeds (:85-91).  Lowering the limit below
+   the current size deletes nothing. */
+int egm_rstore_set_max_retained(egm_rstore* rs, uint64_t max);
 int egm_rstore_match(egm_rstore* rs, const uint8_t* filters_blob, const uint32_t* offsets, uint32_t n,
                      uint64_t now_ms, int mode, egm_result** out);
 

@@ -19,6 +19,16 @@ the same store: the time of egm_rstore_rebuild; then, with the overlay holding
 of K puts (half on topics of the image, half new) and the match after it; and
 the same K puts committed with the overlay cap at 0, where a commit is a
 rebuild.  One JSON line on stdout (bench "retained_live").
+
+--delete F measures delete_message/2 with a wildcard filter on
+two stores of the same topics in one process: F filters (generated C2
+filters and first-word prefixes `w/#`, picked by their match counts to span
+small and large deletes) are deleted one by one, on one store by
+egm_rstore_delete_matching and on the other by the sequence the mirror used
+before that call existed -- egm_rstore_match at now = 0, one egm_rstore_delete
+per matched topic, egm_rstore_commit -- alternating which goes first.  Both
+must drop the same ids.  One JSON line on stdout (bench "retained_delete"),
+also written to profiles/retained_delete.json.
 """
 import argparse
 import json
@@ -40,6 +50,8 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--churn", type=int, default=0, metavar="K",
                     help="measure rebuild, incremental commit of K changes and match against the overlay")
+    ap.add_argument("--delete", type=int, default=0, metavar="F",
+                    help="time F wildcard deletes: the device call against match + per-topic delete + commit")
     a = ap.parse_args()
     from emqx_amd import _lib as L
     from emqx_amd import synth
@@ -56,6 +68,10 @@ def main():
     topics = topics[: a.topics]
     print(f"generated {len(topics)} topics, {flt.n} filters in {time.time() - t0:.1f}s", file=sys.stderr,
           flush=True)
+
+    if a.delete:
+        delete_bench(a, topics, flt)
+        return
 
     rs = RetainedStore(0)
     lib, h = rs.lib, rs.h
@@ -209,6 +225,123 @@ def churn(a, rs, step, topics, flt, build_s):
     }
     print(json.dumps(out))
     assert out["incremental_commit_faster"], "the incremental commit is not faster than the cap-0 commit"
+
+
+def delete_bench(a, topics, flt):
+    """Wildcard deletes: one device call against the match / per-topic delete / commit sequence (--delete)."""
+    import ctypes as C
+    from collections import Counter
+
+    from emqx_amd import _lib as L
+    from emqx_amd.engine import pack_strings
+    from emqx_amd.retainer import RetainedStore
+
+    stores = [RetainedStore(0), RetainedStore(0)]      # [0]: the device call, [1]: the comparison leg
+    lib = stores[0].lib
+    t0 = time.time()
+    for rs in stores:
+        for i, t in enumerate(topics):
+            lib.egm_rstore_put(rs.h, t, len(t), i, 0)
+        rs.rebuild()
+    build_s = (time.time() - t0) / 2
+    print(f"two stores built, {build_s:.1f}s each", file=sys.stderr, flush=True)
+
+    def match_ids(rs, f):
+        blob, off = pack_strings([f])
+        res = C.POINTER(L.egm_result)()
+        rc = lib.egm_rstore_match(rs.h, C.c_void_p(blob.ctypes.data), C.c_void_p(off.ctypes.data), 1, 0,
+                                  L.EGM_RMODE_MATCH, C.byref(res))
+        assert rc == 0, rc
+        nid = int(res.contents.n_ids)
+        ids = np.ctypeslib.as_array(res.contents.ids, shape=(nid,)).copy() if nid else np.zeros(0, np.uint32)
+        lib.egm_result_free(res)
+        return ids
+
+    def device_delete(rs, f):
+        blob, off = pack_strings([f])
+        ids, n = L._u32p(), C.c_uint64()
+        rc = lib.egm_rstore_delete_matching(rs.h, C.c_void_p(blob.ctypes.data), C.c_void_p(off.ctypes.data), 1,
+                                            C.byref(ids), C.byref(n))
+        assert rc == 0, rc
+        out = np.ctypeslib.as_array(ids, shape=(n.value,)).copy() if n.value else np.zeros(0, np.uint32)
+        lib.egm_result_free(ids)
+        return out
+
+    def host_delete(rs, f):
+        ids = match_ids(rs, f)
+        for i in ids.tolist():                         # ids are positions in `topics`
+            t = topics[i]
+            lib.egm_rstore_delete(rs.h, t, len(t))
+        rs.commit()
+        return ids
+
+    # candidates and their sizes on the untouched store
+    firsts = Counter(t.split(b"/", 1)[0] for t in topics)
+    cands = [w + b"/#" for w, _ in firsts.most_common(64)] + [flt[i] for i in range(min(flt.n, 4096))]
+    cands = list(dict.fromkeys(cands))
+    blob, off = pack_strings(cands)
+    res = C.POINTER(L.egm_result)()
+    assert lib.egm_rstore_match(stores[0].h, C.c_void_p(blob.ctypes.data), C.c_void_p(off.ctypes.data), len(cands), 0,
+                                L.EGM_RMODE_MATCH, C.byref(res)) == 0
+    counts = np.ctypeslib.as_array(res.contents.counts, shape=(len(cands),)).copy()
+    lib.egm_result_free(res)
+    order = [int(i) for i in np.argsort(-counts.astype(np.int64), kind="stable") if counts[i] > 0]
+    F = min(a.delete, len(order))
+    # the largest, then an even spread over the rest; under 45 % of the store in all, so that no
+    # commit inside the timed calls is a rebuild by the tombstone rule
+    top, budget = [], int(0.45 * len(topics))
+    for i in order:
+        if len(top) < (F + 1) // 2 and counts[i] <= budget // 2:   # half of what is left: several large ones fit
+            top.append(i)
+            budget -= int(counts[i])
+    budget //= max(1, F - len(top))
+    rest = [i for i in order if i not in top and counts[i] <= budget]
+    pick = top + [rest[(k * len(rest)) // (F - len(top))] for k in range(F - len(top) if rest else 0)]
+    pick = list(dict.fromkeys(pick))
+    warm = next(i for i in reversed(order) if i not in pick)
+    for rs, fn in ((stores[0], device_delete), (stores[1], host_delete)):   # code objects, workspace
+        fn(rs, cands[warm])
+
+    rows = []
+    for k, ci in enumerate(pick):
+        f = cands[ci]
+        legs = [("device_ms", stores[0], device_delete), ("host_ms", stores[1], host_delete)]
+        if k % 2:
+            legs.reverse()
+        row = {"filter": f.decode(errors="replace"), "matched_on_full_store": int(counts[ci])}
+        got = {}
+        for name, rs, fn in legs:
+            t1 = time.perf_counter()
+            got[name] = fn(rs, f)                      # both end synchronised (readback / commit)
+            row[name] = 1e3 * (time.perf_counter() - t1)
+        assert np.array_equal(np.sort(got["device_ms"]), np.sort(got["host_ms"])), f
+        row["ids_deleted"] = int(len(got["device_ms"]))
+        rows.append(row)
+        print(f"{row['filter']}: {row['ids_deleted']} ids, device {row['device_ms']:.3f} ms, "
+              f"match+delete+commit {row['host_ms']:.3f} ms", file=sys.stderr, flush=True)
+    assert stores[0].size() == stores[1].size()
+    big = [r for r in rows if r["ids_deleted"] >= 10_000]
+    dev, host = sum(r["device_ms"] for r in rows), sum(r["host_ms"] for r in rows)
+    out = {
+        "bench": "retained_delete", "metric": "wildcard delete_message: match + per-topic delete + commit over one "
+                                              "egm_rstore_delete_matching call, summed over the filters",
+        "value": host / dev, "unit": "x",
+        "config": {"workload": "c2-shaped", "stored_topics": len(topics), "filters": len(rows),
+                   "timing": "host clock around calls that end in a stream synchronise; one sample per filter "
+                             "(a delete cannot be repeated), legs alternate, one process"},
+        "device_ms_total": dev, "host_ms_total": host, "ids_deleted_total": sum(r["ids_deleted"] for r in rows),
+        "deletes_of_10k_or_more": {"n": len(big), "device_ms": sum(r["device_ms"] for r in big),
+                                   "host_ms": sum(r["host_ms"] for r in big),
+                                   "device_faster_in_all": bool(all(r["device_ms"] < r["host_ms"] for r in big))},
+        "store_build_s": build_s, "by_filter": rows,
+    }
+    line = json.dumps(out)
+    print(line)
+    prof = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
+    with open(os.path.join(prof, "retained_delete.json"), "w") as fh:
+        fh.write(line + "\n")
+    for rs in stores:
+        rs.close()
 
 
 if __name__ == "__main__":
