@@ -27,6 +27,17 @@
  *                      match_routes/1 + dispatch/2 expansion of emqx_broker:publish/1
  *                      (emqx_broker.erl:200-209, 283-308) for a list of topics;
  *                      returns [{[FilterId], [{FilterId, Sub}]}]
+ *   subs_set_dead/3 -> egm_subs_set_dead   (is_process_alive/1 of dispatch/3,
+ *                      emqx_broker.erl:297-302, as a device bitmap)
+ *   share_build/2, share_delta/3 -> egm_share_build / egm_share_apply_delta +
+ *                      egm_share_commit (emqx_shared_sub's member table,
+ *                      emqx_shared_sub.erl:108-118, 292-300)
+ *   dispatch_batch/5 -> egm_match_batch (routes mode) + egm_dispatch_batch:
+ *                      publish_batch/2 with the last step of dispatch/2 and
+ *                      emqx_shared_sub:dispatch/3 done on the device (dead
+ *                      subscribers dropped, one live member picked per group,
+ *                      emqx_shared_sub.erl:239-290; live counts per filter,
+ *                      emqx_broker.erl:283-295)
  *
  * The retained store (apps/emqx_retainer/src/emqx_retainer_mnesia.erl), a
  * resource of its own beside the route context:
@@ -459,6 +470,152 @@ static ERL_NIF_TERM nif_publish_batch(ErlNifEnv* env, int argc, const ERL_NIF_TE
   return enif_make_tuple2(env, ATOM_OK, out);
 }
 
+/* [uint32] -> malloc'd array (*n values); 0 on a bad term */
+static int get_u32_list(ErlNifEnv* env, ERL_NIF_TERM list, uint32_t** out, unsigned* n) {
+  ERL_NIF_TERM head, tail = list;
+  if (!enif_get_list_length(env, list, n)) return 0;
+  *out = (uint32_t*)malloc(sizeof(uint32_t) * (*n ? *n : 1));
+  if (!*out) return 0;
+  for (unsigned i = 0; i < *n; ++i) {
+    unsigned v;
+    if (!enif_get_list_cell(env, tail, &head, &tail) || !enif_get_uint(env, head, &v)) {
+      free(*out);
+      *out = NULL;
+      return 0;
+    }
+    (*out)[i] = v;
+  }
+  return 1;
+}
+
+/* subs_set_dead(Ctx, [Sub], Dead :: 0 | 1) -> ok | {error, _}: the subscribers
+   whose process is gone (1) or back (0); a Sub with bit 31 set is refused. */
+static ERL_NIF_TERM nif_subs_set_dead(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_res_t* r;
+  uint32_t* subs = NULL;
+  unsigned n = 0;
+  int dead;
+  if (argc != 3 || !get_ctx(env, argv[0], &r) || !enif_get_int(env, argv[2], &dead) || (dead != 0 && dead != 1) ||
+      !get_u32_list(env, argv[1], &subs, &n))
+    return enif_make_badarg(env);
+  int rc = egm_subs_set_dead(r->ctx, subs, n, dead);
+  free(subs);
+  return rc ? error_tuple(env, r->ctx, rc) : ATOM_OK;
+}
+
+/* [{FilterId, GroupId, Member}] -> egm_share_member[] (malloc'd; *n rows); 0 on a bad term */
+static int get_triples(ErlNifEnv* env, ERL_NIF_TERM list, egm_share_member** out, unsigned* n) {
+  ERL_NIF_TERM head, tail = list;
+  if (!enif_get_list_length(env, list, n)) return 0;
+  *out = (egm_share_member*)malloc(sizeof(egm_share_member) * (*n ? *n : 1));
+  if (!*out) return 0;
+  for (unsigned i = 0; i < *n; ++i) {
+    const ERL_NIF_TERM* el;
+    int arity;
+    unsigned f, g, m;
+    if (!enif_get_list_cell(env, tail, &head, &tail) || !enif_get_tuple(env, head, &arity, &el) || arity != 3 ||
+        !enif_get_uint(env, el[0], &f) || !enif_get_uint(env, el[1], &g) || !enif_get_uint(env, el[2], &m)) {
+      free(*out);
+      *out = NULL;
+      return 0;
+    }
+    (*out)[i].fid = f;
+    (*out)[i].group = g;
+    (*out)[i].member = m;
+  }
+  return 1;
+}
+
+/* share_build(Ctx, [{FilterId, GroupId, Member}]) -> ok | {error, _}: the
+   $share groups' members, a group's in the order given. */
+static ERL_NIF_TERM nif_share_build(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_res_t* r;
+  egm_share_member* rows = NULL;
+  unsigned n = 0;
+  if (argc != 2 || !get_ctx(env, argv[0], &r) || !get_triples(env, argv[1], &rows, &n)) return enif_make_badarg(env);
+  int rc = egm_share_build(r->ctx, rows, n);
+  free(rows);
+  return rc ? error_tuple(env, r->ctx, rc) : ATOM_OK;
+}
+
+/* share_delta(Ctx, Adds, Dels) -> {ok, Epoch} | {error, _}: the member
+   changes since the last call in one epoch (NET effects, as subs_delta/3: a
+   triple in both lists is refused and nothing is applied). */
+static ERL_NIF_TERM nif_share_delta(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_res_t* r;
+  egm_share_member *add = NULL, *del = NULL;
+  unsigned na = 0, nd = 0;
+  if (argc != 3 || !get_ctx(env, argv[0], &r)) return enif_make_badarg(env);
+  if (!get_triples(env, argv[1], &add, &na)) return enif_make_badarg(env);
+  if (!get_triples(env, argv[2], &del, &nd)) {
+    free(add);
+    return enif_make_badarg(env);
+  }
+  uint64_t epoch = 0;
+  int rc = egm_share_apply_delta(r->ctx, add, na, del, nd);
+  if (!rc) rc = egm_share_commit(r->ctx, &epoch);
+  free(add);
+  free(del);
+  return rc ? error_tuple(env, r->ctx, rc) : enif_make_tuple2(env, ATOM_OK, enif_make_uint64(env, epoch));
+}
+
+/* dispatch_batch(Ctx, [Topic], Keys, Strategy, Seed)
+     -> {ok, [{{[FilterId], [{FilterId, Sub}]}, [{Live, SharedOk}]}]} | {error, _}
+   publish_batch/2's rows with the dead subscribers and the groups without a
+   live member already removed and each group entry replaced by its picked
+   member, and per matched filter (in [FilterId]'s order) its live subscribers
+   and its groups that got a member.  Strategy is EGM_PICK_* (0 random,
+   1 round_robin, 2 sticky, 3 hash, 4 hash_clientid, 5 hash_topic); Keys is one
+   hash per topic (of the client id or the source topic) for the hash
+   strategies, [] otherwise. */
+static ERL_NIF_TERM nif_dispatch_batch(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_res_t* r;
+  uint8_t* blob;
+  uint32_t *off, n, *keys = NULL;
+  unsigned nk = 0;
+  int strategy;
+  ErlNifUInt64 seed;
+  if (argc != 5 || !get_ctx(env, argv[0], &r) || !enif_get_int(env, argv[3], &strategy) ||
+      strategy < EGM_PICK_RANDOM || strategy > EGM_PICK_HASH_TOPIC || !enif_get_uint64(env, argv[4], &seed) ||
+      !get_u32_list(env, argv[2], &keys, &nk))
+    return enif_make_badarg(env);
+  if (!pack_list(env, argv[1], &blob, &off, &n) || (nk != 0 && nk != n) ||
+      (strategy >= EGM_PICK_HASH && nk != n)) {
+    free(keys);
+    return enif_make_badarg(env);
+  }
+  egm_result* res = NULL;
+  egm_dispatch* dl = NULL;
+  int rc = egm_match_batch(r->ctx, blob, off, n, EGM_MODE_ROUTES, &res);
+  free(blob);
+  free(off);
+  if (!rc) rc = egm_dispatch_batch(r->ctx, res, nk ? keys : NULL, strategy, seed, &dl);
+  free(keys);
+  if (rc) {
+    if (res) egm_result_free(res);
+    if (dl) egm_result_free(dl);
+    return error_tuple(env, r->ctx, rc);
+  }
+  ERL_NIF_TERM out = enif_make_list(env, 0);
+  for (uint32_t i = n; i-- > 0;) {
+    ERL_NIF_TERM ids = enif_make_list(env, 0), dv = enif_make_list(env, 0), cn = enif_make_list(env, 0);
+    for (uint64_t k = res->row_ptr[i + 1]; k-- > res->row_ptr[i];) {
+      ids = enif_make_list_cell(env, enif_make_uint(env, res->ids[k]), ids);
+      cn = enif_make_list_cell(
+          env, enif_make_tuple2(env, enif_make_uint(env, dl->entry_live[k]), enif_make_uint(env, dl->entry_shared[k])),
+          cn);
+      for (uint64_t j = dl->entry_pos[k + 1]; j-- > dl->entry_pos[k];)
+        if (dl->sub[j] != EGM_SUB_NONE)
+          dv = enif_make_list_cell(
+              env, enif_make_tuple2(env, enif_make_uint(env, res->ids[k]), enif_make_uint(env, dl->sub[j])), dv);
+    }
+    out = enif_make_list_cell(env, enif_make_tuple2(env, enif_make_tuple2(env, ids, dv), cn), out);
+  }
+  egm_result_free(res);
+  egm_result_free(dl);
+  return enif_make_tuple2(env, ATOM_OK, out);
+}
+
 /* ---- retained store ---- */
 static ERL_NIF_TERM rs_error(ErlNifEnv* env, egm_rstore* rs, int rc) {
   const char* msg = rs ? egm_rstore_last_error(rs) : "egm error";
@@ -618,6 +775,10 @@ static ErlNifFunc nif_funcs[] = {
     {"subs_build", 2, nif_subs_build, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"subs_delta", 3, nif_subs_delta, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"publish_batch", 2, nif_publish_batch, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"subs_set_dead", 3, nif_subs_set_dead, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"share_build", 2, nif_share_build, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"share_delta", 3, nif_share_delta, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"dispatch_batch", 5, nif_dispatch_batch, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     /* the retained store: every call takes the store's lock, which a match or a
        delete holds across its device work, so none runs on a normal scheduler */
     {"rs_open", 1, nif_rs_open, ERL_NIF_DIRTY_JOB_CPU_BOUND},

@@ -41,6 +41,16 @@ EGM_GUARD_LOOP = 8
 
 NONE_ID = 0xFFFFFFFF
 GROUP_BIT = 0x80000000
+EGM_SUB_NONE = 0xFFFFFFFF   # a dispatched delivery slot with no receiver
+
+# egm_dispatch_*'s member pick (EGM_PICK_*), by emqx_amd.broker.STRATEGIES' names
+EGM_PICK_RANDOM = 0
+EGM_PICK_ROUND_ROBIN = 1
+EGM_PICK_STICKY = 2
+EGM_PICK_HASH = 3
+EGM_PICK_HASH_CLIENTID = 4
+EGM_PICK_HASH_TOPIC = 5
+PICK = {"random": 0, "round_robin": 1, "sticky": 2, "hash": 3, "hash_clientid": 4, "hash_topic": 5}
 
 _u8p = C.POINTER(C.c_uint8)
 _u32p = C.POINTER(C.c_uint32)
@@ -66,6 +76,12 @@ class egm_result(C.Structure):
 class egm_delivery(C.Structure):
     _fields_ = [("n_topics", C.c_uint32), ("n_deliveries", C.c_uint64), ("row_ptr", _u64p),
                 ("fid", _u32p), ("sub", _u32p)]
+
+
+class egm_dispatch(C.Structure):
+    _fields_ = [("n_topics", C.c_uint32), ("n_entries", C.c_uint64), ("n_deliveries", C.c_uint64),
+                ("row_ptr", _u64p), ("entry_pos", _u64p), ("sub", _u32p), ("entry_live", _u32p),
+                ("entry_shared", _u32p)]
 
 
 class egm_image_view(C.Structure):
@@ -126,6 +142,16 @@ SIGNATURES = {
     "egm_fanout_device": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P, C.c_uint64]),
     "egm_fanout_device_compact": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P, C.c_uint64]),
     "egm_last_fanout": (C.c_int, [_P, _u64p, _u32p]),
+    "egm_subs_set_dead": (C.c_int, [_P, _P, C.c_uint64, C.c_int]),
+    "egm_share_build": (C.c_int, [_P, _P, C.c_uint64]),
+    "egm_share_apply_delta": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64]),
+    "egm_share_commit": (C.c_int, [_P, _P]),
+    "egm_dispatch_device": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, _P, C.c_int, C.c_uint64, _P, _P, _P, _P,
+                                      C.c_uint64, _P, _P]),
+    "egm_dispatch_batch": (C.c_int, [_P, C.POINTER(egm_result), _P, C.c_int, C.c_uint64,
+                                     C.POINTER(C.POINTER(egm_dispatch))]),
+    "egm_last_dispatch": (C.c_int, [_P, _u64p, _u64p, _u64p, _u64p]),
+    "egm_get_dispatch_timing": (C.c_int, [_P, C.POINTER(C.c_double), _u64p]),
     "egm_shard_merge": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.POINTER(_P), C.c_uint64, _P, _P, _P,
                                   C.c_uint64]),
     "egm_prefix_assign": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),

@@ -23,6 +23,14 @@ with no route, or a local route none of whose subscribers is alive, counts
 ``messages.dropped`` and ``messages.dropped.no_subscribers`` (not for a
 system message, ``inc_dropped_cnt/1`` :311-316, emqx_message.erl:173-177).
 
+``Broker(device_dispatch=True)`` does the last step on the GPU too
+(egm_dispatch_batch: the dead bitmap, the $share member table and the resolve
+pass): the member pick and the live counts are read from the resolved arrays
+instead of being looped over here.  For the hash strategies — whose pick is a
+function of the caller's key alone — it returns exactly what the default path
+returns; random, round_robin and sticky pick by the device's own rules
+(include/emqx_gpu_match.h).
+
 Subscriber sharding ({shard, Topic, I} bags beyond 1024 subscribers,
 emqx_broker.erl:149-157, emqx_broker_helper.erl:82-86) changes only the layout
 of the reference's ETS bags, never the delivery set; the fan-out CSR is the
@@ -128,7 +136,7 @@ class SharedSub:
 
 class Broker:
     def __init__(self, router: Optional[Router] = None, device: int = 0, node: str = "local",
-                 shared_strategy: str = "random", seed: int = 0, shards: int = 32):
+                 shared_strategy: str = "random", seed: int = 0, shards: int = 32, device_dispatch: bool = False):
         if shared_strategy not in STRATEGIES:
             raise ValueError(shared_strategy)
         self.router = router or Router(device=device, node=node)
@@ -149,6 +157,19 @@ class Broker:
         self.subscriptions: Dict[int, set] = {}     # ?SUBSCRIPTION: sub -> {(filter, group or None)}
         self._fid_flt: Dict[int, bytes] = {}         # filter ids seen in subscriber events
         self.dead: set = set()   # subscribers whose process is gone (is_process_alive/1 false)
+        # device_dispatch: liveness, the $share member pick and the route counts
+        # on the GPU (egm_dispatch_batch) instead of the loops below.  The share
+        # table follows subscribe / unsubscribe of $share members by deltas of
+        # (filter id, group id, member) triples, the dead bitmap follows kill /
+        # subscriber_down.
+        self.device_dispatch = device_dispatch
+        self.seed = seed
+        self._dev_shared: Dict[Tuple[int, int], List[int]] = {}   # (filter id, group id) -> members on the device
+        self._share_built = False
+        self._s_touched: Dict[Tuple[int, int], None] = {}         # keys changed since the last publish
+        self._s_removed: set = set()                              # triples removed at some point since then
+        self._dev_dead: set = set()                               # ids marked dead on the device
+        self.last_dispatch: Optional[dict] = None                 # egm_last_dispatch of the last device publish
         self.metrics = {"messages.publish": 0, "messages.dropped": 0, "messages.dropped.no_subscribers": 0,
                         "messages.forward": 0}
 
@@ -181,6 +202,7 @@ class Broker:
                 self.group_ids[group] = len(self.group_names)
                 self.group_names.append(group)
             self.router.do_add_route(flt, ("group", group))
+            self._note_share(flt, group, sub_id, removed=False)
             if len(mem) == 1:   # the (filter, group) entry: one per group, whatever its members
                 self._note(self._d_add, flt, GROUP_BIT | self.group_ids[group])
         self.subscriptions.setdefault(sub_id, set()).add((flt, group))
@@ -206,6 +228,7 @@ class Broker:
             mem = self.shared.get((group, flt), [])
             if sub_id in mem:
                 mem.remove(sub_id)
+                self._note_share(flt, group, sub_id, removed=True)   # (its filter id, before the route may go)
                 if not mem:
                     del self.shared[(group, flt)]
                     self._note(self._d_del, flt, GROUP_BIT | self.group_ids[group])
@@ -254,6 +277,177 @@ class Broker:
         r.m.subs_build(row, flat)
         self._built = True
 
+    def _note_share(self, flt: bytes, group: bytes, member: int, removed: bool):
+        """A $share member event as (filter id, group id, member), the filter
+        id taken now (_note's reason): the member row changes even when the
+        (filter, group) entry of the subscriber table does not."""
+        if not self.device_dispatch:
+            return
+        fid = self.router.filter_id(flt)
+        if fid is None:
+            return
+        self._fid_flt[fid] = flt
+        key = (fid, self.group_ids[group])
+        self._s_touched[key] = None
+        if removed:
+            self._s_removed.add(key + (member,))
+
+    def _share_members(self, fid: int, gid: int) -> List[int]:
+        flt = self._fid_flt[fid]
+        if self.router.filter_id(flt) != fid:   # the filter left the table (its id is not reused)
+            return []
+        return self.shared.get((self.group_names[gid], flt), [])
+
+    def _upload_share(self):
+        """The device share table before a device publish: built once
+        (egm_share_build), then the member changes since the last publish as
+        two deltas — the members gone (or removed and added again: they move
+        to the end of their row, as in the host lists), then the new ones in
+        host order — and one commit, so a key's row keeps the host list's
+        order (the hash picks index into it) and an untouched key its slot."""
+        m = self.router.m
+        if not self._share_built:
+            rows = []
+            self._dev_shared = {}
+            for (group, flt), mem in self.shared.items():
+                fid = self.router.filter_id(flt)
+                self._fid_flt[fid] = flt
+                key = (fid, self.group_ids[group])
+                self._dev_shared[key] = list(mem)
+                rows.extend(key + (x,) for x in mem)
+            m.share_build(rows)
+            self._share_built = True
+        elif self._s_touched:
+            dels, adds = [], []
+            for key in self._s_touched:
+                host = self._share_members(*key)
+                dev = self._dev_shared.get(key, [])
+                keep = [x for x in dev if x in host and key + (x,) not in self._s_removed]
+                dels.extend(key + (x,) for x in dev if x not in keep)
+                adds.extend(key + (x,) for x in host if x not in keep)
+                if host:
+                    self._dev_shared[key] = list(host)
+                else:
+                    self._dev_shared.pop(key, None)
+            if dels:
+                m.share_apply_delta(delete=dels)
+            if adds:
+                m.share_apply_delta(add=adds)
+            if dels or adds:
+                m.share_commit()
+        self._s_touched.clear()
+        self._s_removed.clear()
+
+    def _sync_dead(self, apply: bool):
+        """The device's dead bitmap (egm_subs_set_dead) as ``self.dead`` — or
+        empty: ``publish_batch`` expands to every subscriber whatever its
+        liveness, as the host path does (only ``publish_result`` counts the
+        live ones), so its dispatch runs with nobody marked."""
+        want = self.dead if apply else set()
+        m = self.router.m
+        gone = sorted(self._dev_dead - want)
+        new = sorted(want - self._dev_dead)
+        if gone:
+            m.subs_set_dead(gone, False)
+        if new:
+            m.subs_set_dead(new, True)
+        self._dev_dead = set(want)
+
+    def _msg_keys(self, topics, clientids):
+        """The per-message key of the hash strategies: SharedSub._nth's crc32."""
+        if self.strategy in ("hash", "hash_clientid"):
+            return np.fromiter((zlib.crc32(clientids[k] if clientids else b"") for k in range(len(topics))),
+                               dtype=np.uint32, count=len(topics))
+        if self.strategy == "hash_topic":
+            return np.fromiter((zlib.crc32(t) for t in topics), dtype=np.uint32, count=len(topics))
+        return None
+
+    def _dispatch(self, topics, clientids, liveness: bool):
+        """match + fan-out + egm_dispatch_batch: (match result, delivery rows,
+        each delivery's filter id, its subscriber-table entry, its resolved
+        receiver, the per-entry counts)."""
+        from . import _lib as L
+        self._upload_csr()
+        self._upload_share()
+        self._sync_dead(liveness)
+        r = self.router
+        res = r.match_filters_batch(topics)
+        drow, dfid, raw = r.m.fanout(res)   # the entries as subscribed: which slot is which group's
+        d = r.m.dispatch(res, self._msg_keys(topics, clientids), L.PICK[self.strategy], self.seed)
+        self.last_dispatch = r.m.last_dispatch()
+        assert np.array_equal(d["row_ptr"], drow)
+        return res, drow, dfid, raw, d
+
+    def _publish_batch_device(self, topics, clientids):
+        from . import _lib as L
+        r = self.router
+        res, drow, dfid, raw, d = self._dispatch(topics, clientids, liveness=False)
+        sub = d["sub"]
+        out = []
+        for k in range(len(topics)):
+            dl: List[tuple] = []
+            for j in range(int(drow[k]), int(drow[k + 1])):
+                s = int(sub[j])
+                if s == L.EGM_SUB_NONE:
+                    continue
+                f = r.filter_of(int(dfid[j]))
+                e = int(raw[j])
+                if e & GROUP_BIT:
+                    dl.append(("group", f, self.group_names[e & ~GROUP_BIT], s))
+                else:
+                    dl.append(("sub", f, s))
+            for fid in res.row(k).tolist():
+                f = r.filter_of(fid)
+                for dst in r.routes[f]:
+                    if dst != self.node and not (isinstance(dst, tuple) and dst[0] == "group"):
+                        dl.append(("node", f, dst))
+            out.append(dl)
+        return out
+
+    def _publish_result_batch_device(self, topics, clientids, sys_flags):
+        from . import _lib as L
+        r = self.router
+        res, drow, dfid, raw, d = self._dispatch(topics, clientids, liveness=True)
+        sub, live, shared, epos = d["sub"], d["entry_live"], d["entry_shared"], d["entry_pos"]
+        out = []
+        for k, t in enumerate(topics):
+            sysf = bool(sys_flags[k]) if sys_flags else False
+            if not self._is_sys(t, sysf):
+                self.metrics["messages.publish"] += 1
+            entries: List[tuple] = []
+            served = {}
+            for i in range(int(res.row_ptr[k]), int(res.row_ptr[k + 1])):
+                fid = int(res.ids[i])
+                f = r.filter_of(fid)
+                n_groups = 0
+                for j in range(int(epos[i]), int(epos[i + 1])):
+                    e = int(raw[j])
+                    if e & GROUP_BIT:
+                        n_groups += 1
+                        served[(f, self.group_names[e & ~GROUP_BIT])] = int(sub[j]) != L.EGM_SUB_NONE
+                # entry_shared against the group routes of the filter
+                assert sum(1 for x in r.routes[f] if isinstance(x, tuple) and x[0] == "group") == n_groups
+                assert sum(1 for (ff, _), ok in served.items() if ff == f and ok) == int(shared[i])
+                for dst in r.routes[f]:
+                    if isinstance(dst, tuple) and dst[0] == "group":
+                        continue
+                    if dst == self.node:
+                        n = int(live[i])
+                        if n:
+                            entries.append((dst, f, ("ok", n)))
+                        else:
+                            self._dropped(t, sysf)
+                            entries.append((dst, f, ("error", "no_subscribers")))
+                    else:
+                        self.metrics["messages.forward"] += 1
+                        entries.append((dst, f, "forward"))
+            for key in sorted(served):   # aggre/1 usorts the {Topic, Group} entries
+                entries.append(("share", key[0], ("ok", 1) if served[key] else ("error", "no_subscribers")))
+            if not entries:   # route([], Delivery)
+                self._dropped(t, sysf)
+            out.append(entries)
+        return out
+
     def _apply_ordered(self, add, dele):
         """One delta for the pairs touched since the last publish: each pair's
         net effect, read from the host lists (a pair deleted and added again
@@ -288,6 +482,8 @@ class Broker:
         return self.publish_batch([topic], [clientid])[0]
 
     def publish_batch(self, topics: Sequence[bytes], clientids: Optional[Sequence[bytes]] = None) -> List[List[tuple]]:
+        if self.device_dispatch:
+            return self._publish_batch_device(topics, clientids)
         self._upload_csr()
         r = self.router
         res = r.match_filters_batch(topics)
@@ -329,6 +525,8 @@ class Broker:
     def publish_result_batch(self, topics: Sequence[bytes], clientids: Optional[Sequence[bytes]] = None,
                              sys_flags: Optional[Sequence[bool]] = None) -> List[List[tuple]]:
         """``publish/1`` results for a batch (see the module docstring)."""
+        if self.device_dispatch:
+            return self._publish_result_batch_device(topics, clientids, sys_flags)
         self._upload_csr()
         r = self.router
         res = r.match_filters_batch(topics)

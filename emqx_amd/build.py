@@ -27,7 +27,7 @@ ORACLE = os.path.join(ROOT, "oracle", "liboracle_trie.so")
 # the library's sources (tools/build_variant.py builds the same lists)
 HIP_SOURCES = ("egm_kernels.hip", "egm_pack.hip")
 HOST_SOURCES = ("egm_table.cpp", "egm_bulk.cpp", "egm_capi.cpp", "egm_match.cpp", "egm_pipe.cpp", "egm_fanout.cpp",
-                "egm_part.cpp", "egm_retain.cpp", "egm_dma.cpp")
+                "egm_dispatch.cpp", "egm_part.cpp", "egm_retain.cpp", "egm_dma.cpp")
 HEADERS = [os.path.join(CSRC, f) for f in ("egm_common.h", "egm_table.h", "egm_kernels.h", "egm_dma.h", "egm_pack.h",
                                            "egm_alloc.h", "egm_buf.h", "egm_ctx.h")] + [
     os.path.join(ROOT, "include", "emqx_gpu_match.h")]

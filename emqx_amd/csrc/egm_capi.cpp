@@ -475,8 +475,8 @@ int egm_set_timing(egm_ctx* c, int enable) {
   Timing& T = c->timing;
   T.drain();
   T.on = enable != 0;
-  T.walk.ms = T.fan.ms = 0;
-  T.walk.n = T.fan.n = 0;
+  T.walk.ms = T.fan.ms = T.disp.ms = 0;
+  T.walk.n = T.fan.n = T.disp.n = 0;
   return EGM_OK;
 }
 

@@ -5,6 +5,7 @@
 //   egm_match.cpp   match workspaces, the device match entries, egm_last_*
 //   egm_pipe.cpp    the host pipeline (egm_match_submit / _wait / _batch)
 //   egm_fanout.cpp  the subscriber table and the fan-out
+//   egm_dispatch.cpp the dead bitmap, the share table and the dispatch
 //   egm_part.cpp    shard merge, prefix partition, the host-only image API
 // Everything here is internal to the library (hidden visibility).
 #pragma once
@@ -187,7 +188,7 @@ struct Timing {
     uint64_t n = 0;
   };
   bool on = false;
-  Series walk, fan;
+  Series walk, fan, disp;   // disp: the dispatch's resolve pass alone
   std::vector<hipEvent_t> ev_free;
   hipEvent_t take_event() {
     if (!ev_free.empty()) {
@@ -226,6 +227,7 @@ struct Timing {
   void drain() {
     drain(walk);
     drain(fan);
+    drain(disp);
   }
 };
 
@@ -233,6 +235,41 @@ struct Timing {
 struct PartState {
   DevBuf m_srow, m_tiles, m_tot;   // merge
   DevBuf p_ctr, p_dst;             // prefix routes
+};
+
+// Dispatch on the device (egm_dispatch.cpp): the liveness bitmap
+// (is_process_alive, emqx_broker.erl:297-302) and the $share member table
+// (emqx_shared_sub's ?TAB).  The host keeps both authoritative; a share commit
+// rebuilds the device table into the copy no dispatch in flight reads (the
+// subscriber commit's two-copy scheme).  rr / sticky are indexed by a key's
+// slot, assigned once per key and never reused, and survive commits.
+struct ShareKey {
+  uint32_t slot = 0;
+  std::vector<uint32_t> members;   // in the order given
+};
+struct ShareCopy {
+  DevBuf hash, members, cnt;
+  uint32_t n_buckets = 0;
+};
+struct DispState {
+  // dead bitmap
+  std::vector<uint32_t> dead_host;   // the words, as on the device
+  DevBuf dead;
+  uint64_t dead_words = 0;           // words valid on the device
+  // share table
+  std::unordered_map<uint64_t, ShareKey> keys;   // fid << 32 | group
+  uint32_t next_slot = 0;
+  ShareCopy copy[2];
+  int cur = 0;
+  StreamUses uses[2];                // the queued dispatches that read each copy (and the bitmap, rr, sticky)
+  DevBuf rr, sticky;
+  uint32_t slot_cap = 0;             // entries of rr / sticky
+  uint64_t epoch = 0;
+  // the last dispatch (egm_last_dispatch)
+  DevBuf stats, mkey, epos, elive, eshared;
+  uint64_t seq = 0;                  // dispatches launched: the random pick's sequence number
+  hipStream_t last_stream = nullptr;
+  bool launched = false;
 };
 
 // Subscriber table and fan-out (egm_fanout.cpp).
@@ -318,6 +355,7 @@ struct egm_ctx {
 
   egm::PartState part;   // shard merge and prefix partition routing (egm_part.cpp)
   egm::FanState fan;     // subscriber table and fan-out (egm_fanout.cpp)
+  egm::DispState disp;   // dead bitmap, share table and dispatch (egm_dispatch.cpp)
   egm::Timing timing;
 
   // The per-context workspaces (fan-out, merge, routes) are shared by every
@@ -418,6 +456,10 @@ int run_match(egm_ctx* c, MatchWs& W, const Epoch& ep, const uint8_t* d_blob, co
               int mode, hipStream_t s, uint64_t* d_row, uint32_t* d_ids, uint64_t ids_cap,
               const uint32_t* d_n_live = nullptr, uint32_t* d_topic = nullptr);
 void ws_done(MatchWs& W, hipStream_t s);
+// egm_fanout.cpp: the fan-out of a device match CSR; with `da` the compact form followed by the dispatch's resolve pass
+int run_fanout(egm_ctx* c, const uint64_t* d_mrow, const uint32_t* d_mids, uint64_t mids_len, uint32_t n, hipStream_t s,
+               uint64_t* d_drow, uint32_t* d_fid, uint32_t* d_sub, uint64_t cap, uint64_t* total,
+               uint64_t* d_entry_pos = nullptr, const DispArgs* da = nullptr);
 
 }  // namespace egm
 #pragma GCC visibility pop

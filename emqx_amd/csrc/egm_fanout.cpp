@@ -288,10 +288,11 @@ int egm_subs_last_commit(egm_ctx* c, uint64_t* appended, uint64_t* patched, int*
   return EGM_OK;
 }
 
-static int run_fanout(egm_ctx* c, const uint64_t* d_mrow, const uint32_t* d_mids, uint64_t mids_len, uint32_t n,
-                      hipStream_t s,
-                      uint64_t* d_drow, uint32_t* d_fid, uint32_t* d_sub, uint64_t cap, uint64_t* total,
-                      uint64_t* d_entry_pos = nullptr) {
+}  // extern "C"
+
+int egm::run_fanout(egm_ctx* c, const uint64_t* d_mrow, const uint32_t* d_mids, uint64_t mids_len, uint32_t n,
+                    hipStream_t s, uint64_t* d_drow, uint32_t* d_fid, uint32_t* d_sub, uint64_t cap, uint64_t* total,
+                    uint64_t* d_entry_pos, const DispArgs* da) {
   uint64_t nids = 0;
   hipError_t e = hipMemcpyAsync(&nids, d_mrow + n, 8, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -317,12 +318,23 @@ static int run_fanout(egm_ctx* c, const uint64_t* d_mrow, const uint32_t* d_mids
   // holding it is then protected until this fan-out has read it)
   MatchWs* OW = ord ? &c->ws[c->last_walk.ws] : nullptr;
   if (OW && OW->used && OW->stream != s && OW->ev) hipStreamWaitEvent(s, OW->ev, 0);   // (stream 0 is a stream too)
-  e = launch_fanout(st, d_mrow, d_mids, n, nids, d_drow, d_fid, d_sub, cap, c->fan.dc.as<uint32_t>(),
-                    c->fan.ds0.as<uint4>(), dpos, c->fan.wbase.as<uint64_t>(), c->fan.tiles.as<uint64_t>(),
-                    c->fan.ovf.as<unsigned int>(), s, evp, ord ? c->last_walk.order : nullptr);
+  hipEvent_t evd[2] = {nullptr, nullptr};
+  hipEvent_t* evdp = da ? c->timing.take_pair(evd) : nullptr;
+  if (da)   // the dispatch: the compact fan-out, then the resolve pass over its deliveries
+    e = launch_dispatch(st, d_mrow, d_mids, n, nids, d_drow, d_sub, cap, c->fan.dc.as<uint32_t>(),
+                        c->fan.ds0.as<uint4>(), dpos, c->fan.wbase.as<uint64_t>(), c->fan.tiles.as<uint64_t>(),
+                        c->fan.ovf.as<unsigned int>(), s, evp, ord ? c->last_walk.order : nullptr, *da, evdp);
+  else
+    e = launch_fanout(st, d_mrow, d_mids, n, nids, d_drow, d_fid, d_sub, cap, c->fan.dc.as<uint32_t>(),
+                      c->fan.ds0.as<uint4>(), dpos, c->fan.wbase.as<uint64_t>(), c->fan.tiles.as<uint64_t>(),
+                      c->fan.ovf.as<unsigned int>(), s, evp, ord ? c->last_walk.order : nullptr);
   if (OW) ws_done(*OW, s);
   c->fan.subs.uses[rk].note(s);   // a later subscriber commit must not patch this copy before the fan-out has read it
   c->timing.push_pair(c->timing.fan, evp);
+  if (da) {
+    c->disp.uses[c->disp.cur].note(s);   // ... nor a share commit, a bitmap growth or a cursor growth free what it reads
+    c->timing.push_pair(c->timing.disp, evdp);
+  }
   c->work_end(s);
   c->fan.last_drow = d_drow;
   c->fan.last_topics = n;
@@ -338,6 +350,8 @@ static int run_fanout(egm_ctx* c, const uint64_t* d_mrow, const uint32_t* d_mids
   }
   return EGM_OK;
 }
+
+extern "C" {
 
 int egm_fanout_device(egm_ctx* c, const uint64_t* d_mrow, const uint32_t* d_mids, uint64_t mids_len, uint32_t n,
                       void* hip_stream,

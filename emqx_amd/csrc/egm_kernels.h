@@ -218,6 +218,42 @@ hipError_t launch_fanout(const SubTable& st, const uint64_t* match_row, const ui
                          uint64_t* dpos, uint64_t* wbase, uint64_t* tile_sums, unsigned int* overflow, hipStream_t s,
                          hipEvent_t* ev, const uint64_t* walk_order = nullptr);
 
+// Dispatch (emqx_broker:dispatch/2's liveness check, emqx_broker.erl:297-302,
+// and emqx_shared_sub:pick/6, emqx_shared_sub.erl:239-290): the compact
+// fan-out followed by a resolve pass over its deliveries (k_disp_resolve).
+constexpr uint32_t SUB_NONE = 0xFFFFFFFFu;    // EGM_SUB_NONE: a delivery slot with no receiver
+constexpr uint32_t SHARE_BUCKET = 4;          // 16-B records per 64-B bucket of the share hash
+enum : int { PICK_RANDOM = 0, PICK_ROUND_ROBIN, PICK_STICKY, PICK_HASH, PICK_HASH_CLIENTID, PICK_HASH_TOPIC };
+struct DispTable {
+  const uint32_t* dead;      // bitmap, one bit per subscriber id; a set bit = its process is gone
+  uint32_t dead_words;       // ids past the bitmap are alive
+  const uint4* hash;         // {fid, group, member-row start, slot}; fid SUB_NONE = empty
+  uint32_t n_buckets;        // power of two, or 0: no share table
+  const uint32_t* members;   // the keys' member rows
+  const uint32_t* cnt;       // members of the key in hash record i
+  uint32_t* rr;              // [slot] round-robin cursor
+  uint32_t* sticky;          // [slot] sticky member, SUB_NONE = none
+};
+struct DispArgs {
+  DispTable t;
+  const uint32_t* msg_key;   // [n] per-message key of the hash strategies
+  int strategy;              // PICK_*
+  uint64_t seed, seq;
+  uint32_t* entry_live;      // [nids] live plain subscribers of each match entry
+  uint32_t* entry_shared;    // [nids] its group entries that got a member
+  unsigned long long* stats; // {dead dropped, groups resolved, groups empty, groups missing}, zeroed here
+};
+EGM_HD uint32_t share_bucket(uint32_t fid, uint32_t group, uint32_t n_buckets) {
+  return (uint32_t)(mix64(((uint64_t)fid << 32) | group) & (n_buckets - 1));
+}
+// launch_fanout's compact form (deliv_fid == nullptr, the caller's dpos), then
+// the resolve pass; ev_disp (optional) brackets the resolve pass alone.
+hipError_t launch_dispatch(const SubTable& st, const uint64_t* match_row, const uint32_t* match_ids, uint32_t n,
+                           uint64_t nids, uint64_t* deliv_row, uint32_t* deliv_sub, uint64_t deliv_cap, uint32_t* wsum,
+                           uint4* dsrc, uint64_t* dpos, uint64_t* wbase, uint64_t* tile_sums, unsigned int* overflow,
+                           hipStream_t s, hipEvent_t* ev, const uint64_t* walk_order, const DispArgs& da,
+                           hipEvent_t* ev_disp);
+
 // Filter-shard merge: G shard CSRs of one topic batch ->
 // one CSR, per topic shard 0's ids first.  cnt is [G][n]; src[g].ids holds
 // shard g's ids back to back (device array of G pointers); srow is scratch

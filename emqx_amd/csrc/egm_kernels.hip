@@ -2469,6 +2469,284 @@ hipError_t launch_fanout(const SubTable& st, const uint64_t* mrow, const uint32_
   return hipGetLastError();
 }
 
+// -------------------------------------------------------------- dispatch ----
+// The last step of emqx_broker:dispatch/2 and emqx_shared_sub:dispatch/3 on
+// the compact fan-out's deliveries, in place: a subscriber whose process is
+// gone (is_process_alive, emqx_broker.erl:297-302) becomes SUB_NONE, a
+// (filter, group) entry becomes one live member of the group picked by the
+// strategy (emqx_shared_sub.erl:239-290) or SUB_NONE, and each match entry
+// gets its live-subscriber and served-group counts (emqx_broker.erl:283-295).
+// Decomposed like k_fan_fill: one wave per window of 64 match entries, whose
+// deliveries are the contiguous range [dpos[w0], dpos[w0 + 64]); lanes stride
+// over them and find the owning entry by the 6-step search over the window's
+// positions in LDS.  A plain subscriber costs one bitmap word (the bitmap is
+// small: L2/MALL) and is rewritten only when dead.  A group entry probes the
+// share hash (bounded by the bucket count); up to DISP_BIG members its lane
+// resolves it alone in two passes over the row (count live, take the k-th
+// live), a larger group is resolved by the whole wave with a ballot over
+// member liveness (FAN_BIG's split).
+constexpr int DISP_WAVES = 4;
+constexpr uint32_t DISP_BIG = 64;   // a group of more members is resolved by the whole wave
+
+struct DispLds {   // one wave's window of 64 entries
+  uint64_t pos[65];
+  uint32_t fid[64], live[64], shared[64];
+};
+
+__device__ __forceinline__ bool disp_dead(const DispTable& t, uint32_t s) {
+  const uint32_t w = s >> 5;
+  return w < t.dead_words && ((t.dead[w] >> (s & 31u)) & 1u);
+}
+
+// splitmix64's finaliser over (seed, dispatch sequence number, delivery index)
+__device__ __forceinline__ uint64_t disp_mix(uint64_t seed, uint64_t seq, uint64_t d) {
+  uint64_t z = seed + 0x9E3779B97F4A7C15ull * (seq + 1) + 0xD1B54A32D192ED03ull * (d + 1);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// The record of (fid, group) in the share hash: its index, or SUB_NONE.  Linear
+// probing over 64-B buckets; a bucket with a free record ends the chain (the
+// table is rebuilt whole, nothing is ever deleted from it).
+__device__ __forceinline__ uint32_t share_find(const DispTable& t, uint32_t fid, uint32_t group, uint4* rec) {
+  if (!t.n_buckets) return SUB_NONE;
+  uint32_t b = share_bucket(fid, group, t.n_buckets);
+  for (uint32_t step = 0; step < t.n_buckets; ++step) {
+    bool open = false;
+#pragma unroll
+    for (uint32_t k = 0; k < SHARE_BUCKET; ++k) {
+      const uint4 r = t.hash[(uint64_t)b * SHARE_BUCKET + k];
+      if (r.x == fid && r.y == group) {
+        *rec = r;
+        return b * SHARE_BUCKET + k;
+      }
+      open |= r.x == SUB_NONE;
+    }
+    if (open) break;
+    b = (b + 1) & (t.n_buckets - 1);
+  }
+  return SUB_NONE;
+}
+
+// The topic of match entry e: the last t with mrow[t] <= e (rows may be empty).
+__device__ __forceinline__ uint32_t disp_topic_of(const uint64_t* __restrict__ mrow, uint32_t n, uint64_t e) {
+  uint32_t lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (mrow[mid] <= e) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// The pick among n_live (> 0) live members of the key in `slot`: an index.
+__device__ __forceinline__ uint32_t disp_index(const DispArgs& a, uint32_t n_live, uint32_t slot, uint32_t key,
+                                               uint64_t d) {
+  switch (a.strategy) {
+    case PICK_ROUND_ROBIN: return atomicAdd(&a.t.rr[slot], 1u) % n_live;
+    case PICK_HASH:
+    case PICK_HASH_CLIENTID:
+    case PICK_HASH_TOPIC: return key % n_live;
+    default: return (uint32_t)(disp_mix(a.seed, a.seq, d) % n_live);   // random, and sticky's new pick
+  }
+}
+
+// pick(sticky, ...) past the first check (emqx_shared_sub.erl:244-252): the
+// sticky member `seen` is gone, `c` is the new pick; the first delivery to
+// swap it in decides for the others.
+__device__ __forceinline__ uint32_t disp_sticky_settle(const DispTable& t, uint32_t slot, uint32_t seen, uint32_t c) {
+  const uint32_t old = atomicCAS(&t.sticky[slot], seen, c);
+  if (old == seen) return c;
+  return (old != SUB_NONE && !disp_dead(t, old)) ? old : c;
+}
+
+// A group of at most DISP_BIG members, by one lane.
+__device__ __forceinline__ uint32_t disp_group_lane(const DispArgs& a, uint32_t start, uint32_t cnt, uint32_t slot,
+                                                    uint32_t key, uint64_t d) {
+  const DispTable& t = a.t;
+  const bool sticky = a.strategy == PICK_STICKY;
+  const uint32_t st = sticky ? __hip_atomic_load(&t.sticky[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : SUB_NONE;
+  uint32_t n_live = 0;
+  bool st_ok = false;
+  for (uint32_t j = 0; j < cnt; ++j) {
+    const uint32_t m = t.members[start + j];
+    const bool al = !disp_dead(t, m);
+    n_live += al ? 1u : 0u;
+    st_ok |= al && m == st;
+  }
+  if (sticky && st_ok) return st;
+  if (!n_live) return SUB_NONE;
+  uint32_t k = disp_index(a, n_live, slot, key, d), c = SUB_NONE;
+  for (uint32_t j = 0; j < cnt; ++j) {
+    const uint32_t m = t.members[start + j];
+    if (disp_dead(t, m)) continue;
+    if (k == 0) {
+      c = m;
+      break;
+    }
+    --k;
+  }
+  // (a member that died between the passes: the liveness check races, as the reference's does)
+  if (c == SUB_NONE) return SUB_NONE;
+  return sticky ? disp_sticky_settle(t, slot, st, c) : c;
+}
+
+// A group of more than DISP_BIG members, by the whole wave, for lane `o`'s
+// delivery; every lane passes the same arguments and gets the same result.
+__device__ __forceinline__ uint32_t disp_group_wave(const DispArgs& a, uint32_t lane, uint32_t o, uint32_t start,
+                                                    uint32_t cnt, uint32_t slot, uint32_t key, uint64_t d) {
+  const DispTable& t = a.t;
+  const bool sticky = a.strategy == PICK_STICKY;
+  uint32_t st = SUB_NONE;
+  if (sticky) {
+    st = lane == o ? __hip_atomic_load(&t.sticky[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+    st = __shfl(st, (int)o, 64);
+  }
+  uint32_t n_live = 0;
+  bool st_ok = false;
+  for (uint32_t j0 = 0; j0 < cnt; j0 += 64) {
+    const bool in = j0 + lane < cnt;
+    const uint32_t m = in ? t.members[start + j0 + lane] : 0u;
+    const bool al = in && !disp_dead(t, m);
+    n_live += popc(__ballot(al));
+    st_ok |= __ballot(al && m == st) != 0;
+  }
+  if (sticky && st_ok) return st;
+  if (!n_live) return SUB_NONE;
+  uint32_t rem = lane == o ? disp_index(a, n_live, slot, key, d) : 0u;   // (the cursor advances once)
+  rem = __shfl(rem, (int)o, 64);
+  uint32_t c = SUB_NONE;
+  for (uint32_t j0 = 0; j0 < cnt; j0 += 64) {
+    const bool in = j0 + lane < cnt;
+    const uint32_t m = in ? t.members[start + j0 + lane] : 0u;
+    const bool al = in && !disp_dead(t, m);
+    const uint64_t bal = __ballot(al);
+    const uint32_t pc = popc(bal);
+    if (rem < pc) {
+      const uint64_t hit = __ballot(al && mbcnt(bal) == rem);
+      c = __shfl(m, (int)__builtin_ctzll(hit), 64);
+      break;
+    }
+    rem -= pc;
+  }
+  if (c == SUB_NONE) return SUB_NONE;
+  if (sticky) {
+    uint32_t r = lane == o ? disp_sticky_settle(t, slot, st, c) : 0u;
+    c = __shfl(r, (int)o, 64);
+  }
+  return c;
+}
+
+__global__ __launch_bounds__(64 * DISP_WAVES) void k_disp_resolve(const uint64_t* __restrict__ mrow, uint32_t n,
+                                                                  const uint32_t* __restrict__ mids, uint64_t nids,
+                                                                  const uint64_t* __restrict__ dpos,
+                                                                  uint32_t* __restrict__ dsub,
+                                                                  const unsigned int* __restrict__ overflow,
+                                                                  DispArgs a) {
+  if (*overflow) return;   // the fan-out did not fit deliv_cap: nothing is resolved
+  __shared__ DispLds S[DISP_WAVES];
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  DispLds& L = S[wave];
+  const bool hashed = a.strategy >= PICK_HASH;
+  const uint64_t nwin = (nids + 63) / 64;
+  uint32_t n_dead = 0, n_res = 0, n_empty = 0, n_miss = 0;
+  for (uint64_t w = (uint64_t)blockIdx.x * DISP_WAVES + wave; w < nwin; w += (uint64_t)gridDim.x * DISP_WAVES) {
+    const uint64_t w0 = w * 64;
+    L.pos[lane] = dpos[min(w0 + lane, nids)];
+    if (lane == 0) L.pos[64] = dpos[min(w0 + 64, nids)];
+    L.fid[lane] = mids[min(w0 + lane, nids - 1)];
+    L.live[lane] = 0;
+    L.shared[lane] = 0;
+    wave_sync();
+    const uint64_t end = L.pos[64];
+    for (uint64_t d0 = L.pos[0]; d0 < end; d0 += 64) {
+      const uint64_t d = d0 + lane;
+      const bool act = d < end;
+      const uint32_t s = act ? dsub[d] : 0u;
+      // the last k with pos[k] <= d (an entry without deliveries shares its successor's position)
+      uint32_t k = 0;
+#pragma unroll
+      for (uint32_t b = 32; b; b >>= 1)
+        if (L.pos[k + b] <= d) k += b;
+      const bool grp = act && (s & 0x80000000u);
+      if (act && !grp) {
+        if (disp_dead(a.t, s)) {
+          dsub[d] = SUB_NONE;
+          ++n_dead;
+        } else {
+          atomicAdd(&L.live[k], 1u);
+        }
+      }
+      uint32_t start = 0, cnt = 0, slot = 0, key = 0;
+      bool found = false;
+      if (grp) {
+        uint4 rec;
+        const uint32_t ri = share_find(a.t, L.fid[k], s & 0x7FFFFFFFu, &rec);
+        if (ri != SUB_NONE) {
+          found = true;
+          start = rec.z;
+          slot = rec.w;
+          cnt = a.t.cnt[ri];
+          if (hashed) key = a.msg_key[disp_topic_of(mrow, n, w0 + k)];
+        } else {
+          dsub[d] = SUB_NONE;
+          ++n_miss;
+        }
+      }
+      uint32_t res = SUB_NONE;
+      if (found && cnt <= DISP_BIG) res = disp_group_lane(a, start, cnt, slot, key, d);
+      for (uint64_t mb = __ballot(found && cnt > DISP_BIG); mb; mb &= mb - 1) {
+        const uint32_t o = (uint32_t)__builtin_ctzll(mb);
+        const uint32_t r = disp_group_wave(a, lane, o, __shfl(start, (int)o, 64), __shfl(cnt, (int)o, 64),
+                                           __shfl(slot, (int)o, 64), __shfl(key, (int)o, 64), d0 + o);
+        if (lane == o) res = r;
+      }
+      if (found) {
+        dsub[d] = res;   // bit 31 clear, or SUB_NONE
+        if (res != SUB_NONE) {
+          atomicAdd(&L.shared[k], 1u);
+          ++n_res;
+        } else {
+          ++n_empty;
+        }
+      }
+    }
+    wave_sync();
+    if (w0 + lane < nids) {   // each entry belongs to exactly one window: written once, coalesced
+      a.entry_live[w0 + lane] = L.live[lane];
+      a.entry_shared[w0 + lane] = L.shared[lane];
+    }
+    wave_sync();
+  }
+  uint32_t v[4] = {n_dead, n_res, n_empty, n_miss};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+#pragma unroll
+    for (int dd = 32; dd >= 1; dd >>= 1) v[q] += __shfl_xor(v[q], dd, 64);
+    if (lane == 0 && v[q]) atomicAdd(&a.stats[q], (unsigned long long)v[q]);
+  }
+}
+
+hipError_t launch_dispatch(const SubTable& st, const uint64_t* mrow, const uint32_t* mids, uint32_t n, uint64_t nids,
+                           uint64_t* drow, uint32_t* dsub, uint64_t cap, uint32_t* wsum, uint4* ds0, uint64_t* dpos,
+                           uint64_t* wbase, uint64_t* tile_sums, unsigned int* overflow, hipStream_t s, hipEvent_t* ev,
+                           const uint64_t* walk_order, const DispArgs& da, hipEvent_t* ev_disp) {
+  hipError_t e = launch_fanout(st, mrow, mids, n, nids, drow, nullptr, dsub, cap, wsum, ds0, dpos, wbase, tile_sums,
+                               overflow, s, ev, walk_order);
+  if (e != hipSuccess) return e;
+  if ((e = hipMemsetAsync(da.stats, 0, 4 * sizeof(unsigned long long), s)) != hipSuccess) return e;
+  if (ev_disp) hipEventRecord(ev_disp[0], s);
+  if (nids) {
+    const uint64_t nwin = (nids + 63) / 64;
+    const uint32_t g = (uint32_t)std::min<uint64_t>((nwin + DISP_WAVES - 1) / DISP_WAVES, 16384);
+    hipLaunchKernelGGL(k_disp_resolve, dim3(g), dim3(64 * DISP_WAVES), 0, s, mrow, n, mids, nids, dpos, dsub, overflow,
+                       da);
+  }
+  if (ev_disp) hipEventRecord(ev_disp[1], s);
+  return hipGetLastError();
+}
+
 // ----------------------------------------------------------- shard merge ----
 // Filter-sharded layout: rank 0 holds every shard's CSR for the
 // same topic batch as counts cnt[g][t] plus the shard's ids back to back.

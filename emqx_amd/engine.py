@@ -380,6 +380,81 @@ class GpuMatcher:
         self._check(self.lib.egm_last_fanout(self.ctx, C.byref(tot), C.byref(ovf)), "egm_last_fanout")
         return {"deliveries": tot.value, "overflow": ovf.value}
 
+    # -- dispatch on the device -------------------------------------------------
+    def subs_set_dead(self, subs, dead: bool = True):
+        """egm_subs_set_dead: mark subscriber ids dead (their process is gone) or alive again."""
+        a = np.ascontiguousarray(np.asarray(subs, dtype=np.uint32).reshape(-1))
+        self._check(self.lib.egm_subs_set_dead(self.ctx, _ptr(a) if len(a) else None, len(a), 1 if dead else 0),
+                    "egm_subs_set_dead")
+
+    @staticmethod
+    def _triples(rows) -> np.ndarray:
+        return np.ascontiguousarray(np.asarray(rows, dtype=np.uint32).reshape(-1, 3))
+
+    def share_build(self, rows=()):
+        """egm_share_build: the $share member table from (filter id, group id, member) triples."""
+        a = self._triples(rows)
+        self._check(self.lib.egm_share_build(self.ctx, _ptr(a) if len(a) else None, len(a)), "egm_share_build")
+
+    def share_apply_delta(self, add=(), delete=()):
+        """egm_share_apply_delta: (filter id, group id, member) triples to add / remove (net changes)."""
+        a, d = self._triples(add), self._triples(delete)
+        self._check(self.lib.egm_share_apply_delta(self.ctx, _ptr(a) if len(a) else None, len(a),
+                                                   _ptr(d) if len(d) else None, len(d)), "egm_share_apply_delta")
+
+    def share_commit(self) -> int:
+        ep = C.c_uint64()
+        self._check(self.lib.egm_share_commit(self.ctx, C.byref(ep)), "egm_share_commit")
+        return ep.value
+
+    def dispatch_device(self, d_mrow: int, d_mids: int, mids_len: int, n: int, d_msg_key: int, strategy: int,
+                        seed: int, stream: int, d_drow: int, d_entry_pos: int, d_sub: int, cap: int,
+                        d_entry_live: int, d_entry_shared: int):
+        """egm_dispatch_device: the compact fan-out + the resolve pass (raw device pointers)."""
+        self._check(self.lib.egm_dispatch_device(self.ctx, d_mrow, d_mids, mids_len, n, d_msg_key or None, strategy,
+                                                 seed, stream or None, d_drow, d_entry_pos, d_sub, cap, d_entry_live,
+                                                 d_entry_shared), "egm_dispatch_device")
+
+    def dispatch(self, m: MatchResult, msg_key: Optional[np.ndarray] = None, strategy: int = L.EGM_PICK_RANDOM,
+                 seed: int = 0) -> dict:
+        """egm_dispatch_batch: resolved deliveries of a host match result — row_ptr
+        u64[n+1], entry_pos u64[n_ids+1], sub u32 (EGM_SUB_NONE: no receiver),
+        entry_live / entry_shared u32[n_ids]."""
+        n = len(m.row_ptr) - 1
+        counts = np.diff(m.row_ptr).astype(np.uint32)
+        r = L.egm_result(n, len(m.ids), counts.ctypes.data_as(L._u32p),
+                         m.row_ptr.ctypes.data_as(L._u64p), m.ids.ctypes.data_as(L._u32p),
+                         m.flags.ctypes.data_as(L._u8p), m.epoch, m.visited, m.n_heavy, m.n_error)
+        key = None if msg_key is None else np.ascontiguousarray(msg_key, dtype=np.uint32)
+        if key is not None and len(key) != n:
+            raise ValueError("msg_key: one key per topic")
+        out = C.POINTER(L.egm_dispatch)()
+        self._check(self.lib.egm_dispatch_batch(self.ctx, C.byref(r), _ptr(key), strategy, seed, C.byref(out)),
+                    "egm_dispatch_batch")
+        try:
+            d = out.contents
+            tot, ne = int(d.n_deliveries), int(d.n_entries)
+
+            def arr(p, k, dt):
+                return np.ctypeslib.as_array(p, shape=(k,)).copy() if k else np.zeros(0, dt)
+
+            return {"row_ptr": arr(d.row_ptr, n + 1, np.uint64), "entry_pos": arr(d.entry_pos, ne + 1, np.uint64),
+                    "sub": arr(d.sub, tot, np.uint32), "entry_live": arr(d.entry_live, ne, np.uint32),
+                    "entry_shared": arr(d.entry_shared, ne, np.uint32)}
+        finally:
+            self.lib.egm_result_free(out)
+
+    def last_dispatch(self) -> dict:
+        """Counters of the last dispatch (synchronises it)."""
+        v = [C.c_uint64() for _ in range(4)]
+        self._check(self.lib.egm_last_dispatch(self.ctx, *[C.byref(x) for x in v]), "egm_last_dispatch")
+        return dict(zip(("dead_dropped", "groups_resolved", "groups_empty", "missing_groups"),
+                        (x.value for x in v)))
+
+    def dispatch_timing(self) -> dict:
+        ms, k = C.c_double(), C.c_uint64()
+        self._check(self.lib.egm_get_dispatch_timing(self.ctx, C.byref(ms), C.byref(k)), "egm_get_dispatch_timing")
+        return {"resolve_ms": ms.value, "resolve_launches": k.value}
 
     # -- multi-GPU filter shards --------------------------------------------------
     def shard_merge(self, n_shards: int, n: int, d_counts: int, d_shard_ids: Sequence[int], total: int,

@@ -19,6 +19,8 @@
 
 -export([open/1, build/2, apply_delta/3, match_batch/3, submit/3, wait/2, cancel/2, subs_build/2,
          subs_delta/3, publish_batch/2]).
+%% dispatch on the device: liveness, $share member pick, route counts
+-export([subs_set_dead/3, share_build/2, share_delta/3, dispatch_batch/5]).
 %% the retained store (emqx_retainer_mnesia's table mirrored on the device)
 -export([rs_open/1, rs_put/4, rs_delete/2, rs_delete_matching/2, rs_set_max_retained/2, rs_clean/1, rs_size/1, rs_commit/1,
          rs_clear_expired/2, rs_match/4]).
@@ -48,6 +50,17 @@ cancel(_Ctx, _Ticket) -> erlang:nif_error(nif_not_loaded).
 subs_build(_Ctx, _SubsByFilterId) -> erlang:nif_error(nif_not_loaded).
 subs_delta(_Ctx, _Adds, _Dels) -> erlang:nif_error(nif_not_loaded).
 publish_batch(_Ctx, _Topics) -> erlang:nif_error(nif_not_loaded).
+%% Dispatch on the device (emqx_broker:dispatch/2's is_process_alive check,
+%% emqx_broker.erl:297-302; emqx_shared_sub:pick/6, emqx_shared_sub.erl:239-290):
+%% subs_set_dead/3 marks subscriber ids dead (1) or alive (0); share_build/2 and
+%% share_delta/3 keep the groups' members as {FilterId, GroupId, Member} triples;
+%% dispatch_batch/5 -> {ok, [{{[FilterId], [{FilterId, Sub}]}, [{Live, SharedOk}]}]},
+%% the deliveries already resolved (Strategy 0 random, 1 round_robin, 2 sticky,
+%% 3 hash, 4 hash_clientid, 5 hash_topic; Keys one hash per topic or []).
+subs_set_dead(_Ctx, _Subs, _Dead) -> erlang:nif_error(nif_not_loaded).
+share_build(_Ctx, _Members) -> erlang:nif_error(nif_not_loaded).
+share_delta(_Ctx, _Adds, _Dels) -> erlang:nif_error(nif_not_loaded).
+dispatch_batch(_Ctx, _Topics, _Keys, _Strategy, _Seed) -> erlang:nif_error(nif_not_loaded).
 %% Retained store: topic -> {MsgId, ExpiryMs}; the messages stay with the caller.
 %% rs_put/4 -> ok | {error, full}; rs_delete_matching/2 and rs_clear_expired/2
 %% -> {ok, [MsgId]} (the dropped ids); rs_match/4 -> {ok, [[MsgId]]} per filter,

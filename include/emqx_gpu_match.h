@@ -354,6 +354,99 @@ int egm_fanout_device_compact(egm_ctx* ctx, const uint64_t* d_match_row, const u
    rerun with deliv_cap >= n_deliveries). */
 int egm_last_fanout(egm_ctx* ctx, uint64_t* n_deliveries, uint32_t* overflow);
 
+/* ---- dispatch on the device: liveness, $share member pick, route counts ----
+   The last step of emqx_broker:dispatch/2 (apps/emqx/src/emqx_broker.erl:
+   283-308) and emqx_shared_sub:dispatch/3 (emqx_shared_sub.erl:120-134,
+   239-290) on the fan-out's deliveries: a subscriber whose process is gone is
+   dropped (is_process_alive, emqx_broker.erl:297-302), a (filter, group) entry
+   is replaced by one live member of the group picked by the strategy
+   (pick/6, do_pick/6, pick_subscriber/6, emqx_shared_sub.erl:239-290), and the
+   live subscribers per matched filter are counted ({ok, N} |
+   {error, no_subscribers}, emqx_broker.erl:283-295).  The ack/nack redispatch
+   of dispatch/4 needs the sessions' answers and stays with the caller. */
+#define EGM_SUB_NONE 0xFFFFFFFFu   /* a delivery slot with no receiver: consumers skip it */
+/* The member pick, one per call (emqx_shared_sub.erl:268-290; `hash` is
+   hash_clientid).  The hash picks are live[key % n_live] with the caller's
+   per-message key; random is a splitmix of (seed, the context's dispatch
+   sequence number, delivery index); round_robin advances one cursor per
+   (filter, group) on the device; sticky keeps a member until it is gone
+   (pick(sticky, ...), :239-252). */
+#define EGM_PICK_RANDOM 0
+#define EGM_PICK_ROUND_ROBIN 1
+#define EGM_PICK_STICKY 2
+#define EGM_PICK_HASH 3
+#define EGM_PICK_HASH_CLIENTID 4
+#define EGM_PICK_HASH_TOPIC 5
+/* Mark subscribers dead (dead != 0) or alive again (is_process_alive/1,
+   emqx_broker.erl:297-302): a device bitmap of one bit per subscriber id,
+   grown to the largest id ever marked (an id near 2^31 allocates 256 MB; ids
+   are expected to be dense and small); an id past it is alive.  An id with
+   bit 31 set is refused with EGM_E_INVAL and nothing is applied.  Visible to
+   every dispatch submitted after the call returns; one already launched may
+   see either state (the reference's check races the same way). */
+int egm_subs_set_dead(egm_ctx* ctx, const uint32_t* subs, uint64_t n, int dead);
+/* The members of the $share groups (emqx_shared_sub's ?TAB,
+   emqx_shared_sub.erl:108-118, 292-300), keyed by (filter id, group id — the
+   fan-out entry without its bit 31).  egm_share_build replaces the table and
+   publishes it; a key's member order is the order given and a duplicate
+   triple is kept once.  egm_share_apply_delta stages NET changes under
+   egm_subs_apply_delta's contract (a triple in both lists: EGM_E_INVAL,
+   nothing applied; removing an absent triple does nothing) and
+   egm_share_commit publishes them in one epoch: the table is rebuilt into the
+   device copy no dispatch in flight reads, so dispatches already launched
+   keep the membership they started with.  A key whose last member leaves is
+   gone; added again it is a new key (its round-robin cursor and sticky
+   member start afresh).  A member id has bit 31 clear. */
+typedef struct egm_share_member {
+  uint32_t fid;      /* filter id */
+  uint32_t group;    /* $share group id (bit 31 ignored) */
+  uint32_t member;   /* subscriber id */
+} egm_share_member;
+int egm_share_build(egm_ctx* ctx, const egm_share_member* rows, uint64_t n);
+int egm_share_apply_delta(egm_ctx* ctx, const egm_share_member* add, uint64_t n_add, const egm_share_member* del,
+                          uint64_t n_del);
+int egm_share_commit(egm_ctx* ctx, uint64_t* epoch);
+/* egm_fanout_device_compact followed by the resolve pass over its deliveries
+   (same stream, overflow and d_deliv_row / d_entry_pos rules): d_sub[k] is a
+   live subscriber id, a group's picked member (bit 31 clear), or EGM_SUB_NONE
+   (a dead subscriber; a group with no live member, or one absent from the
+   share table — a context with no share table resolves every group to NONE).
+   d_entry_live[i] / d_entry_shared[i] (match_ids entries each) receive the
+   live plain subscribers of match entry i and its group entries that got a
+   member.  d_msg_key[n_topics] is the caller's hash of each message's client
+   id (hash / hash_clientid) or source topic (hash_topic); NULL otherwise — a
+   hash strategy without it is EGM_E_INVAL.  When deliv_cap is too small
+   nothing is resolved, nothing is written past deliv_cap, the per-entry
+   arrays are untouched and egm_last_fanout reports the total.
+   EGM_E_STATE before egm_subs_build. */
+int egm_dispatch_device(egm_ctx* ctx, const uint64_t* d_match_row, const uint32_t* d_match_ids,
+                        uint64_t match_ids_len, uint32_t n_topics, const uint32_t* d_msg_key, int strategy,
+                        uint64_t seed, void* hip_stream, uint64_t* d_deliv_row, uint64_t* d_entry_pos, uint32_t* d_sub,
+                        uint64_t deliv_cap, uint32_t* d_entry_live, uint32_t* d_entry_shared);
+/* Host form: the plain result form only (as egm_fanout_batch); free with
+   egm_result_free.  Delivery k of match entry i (filter matched->ids[i]) is
+   sub[entry_pos[i] + k]. */
+typedef struct egm_dispatch {
+  uint32_t n_topics;
+  uint64_t n_entries;      /* matched ids of the batch */
+  uint64_t n_deliveries;
+  uint64_t* row_ptr;       /* [n_topics+1] deliveries per topic */
+  uint64_t* entry_pos;     /* [n_entries+1] */
+  uint32_t* sub;           /* [n_deliveries] resolved receivers (EGM_SUB_NONE: none) */
+  uint32_t* entry_live;    /* [n_entries] */
+  uint32_t* entry_shared;  /* [n_entries] */
+} egm_dispatch;
+int egm_dispatch_batch(egm_ctx* ctx, const egm_result* matched, const uint32_t* msg_key, int strategy, uint64_t seed,
+                       egm_dispatch** out);
+/* Synchronises the last dispatch and reports its counters: dead subscribers
+   dropped, group entries that got a member, group entries whose members are
+   all dead, group entries absent from the share table. */
+int egm_last_dispatch(egm_ctx* ctx, uint64_t* dead_dropped, uint64_t* groups_resolved, uint64_t* groups_empty,
+                      uint64_t* missing_groups);
+/* Accumulated time (ms) and launches of the resolve pass alone, under
+   egm_set_timing (the fan-out before it is counted in egm_get_timing). */
+int egm_get_dispatch_timing(egm_ctx* ctx, double* resolve_ms, uint64_t* launches);
+
 /* ---- multi-GPU filter sharding ----
    Merge the match results of one topic batch against n_shards disjoint filter
    shards (each matched on its own GPU, gathered here over RCCL) into one CSR:
