@@ -616,6 +616,115 @@ static ERL_NIF_TERM nif_dispatch_batch(ErlNifEnv* env, int argc, const ERL_NIF_T
   return enif_make_tuple2(env, ATOM_OK, out);
 }
 
+/* ---- cluster routes ---- */
+_Static_assert(sizeof(egm_route_pair) == sizeof(egm_sub_pair), "get_pairs fills either pair");
+/* erl_nif.h's own declaration, repeated (a compatible redeclaration): forward/2 is the one entry that builds a binary */
+extern unsigned char* enif_make_new_binary(ErlNifEnv* env, size_t size, ERL_NIF_TERM* termp);
+
+/* routes_build(Ctx, [Mask], SelfNode) -> ok | {error, _}: the route-node table,
+   one 64-bit node mask per filter id (bit N: a route {Filter, node N}). */
+static ERL_NIF_TERM nif_routes_build(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_res_t* r;
+  unsigned n, self;
+  if (argc != 3 || !get_ctx(env, argv[0], &r) || !enif_get_list_length(env, argv[1], &n) ||
+      !enif_get_uint(env, argv[2], &self))
+    return enif_make_badarg(env);
+  uint64_t* masks = (uint64_t*)malloc(sizeof(uint64_t) * (n ? n : 1));
+  if (!masks) return enif_make_badarg(env);
+  ERL_NIF_TERM head, tail = argv[1];
+  for (unsigned i = 0; i < n; ++i) {
+    ErlNifUInt64 m;
+    if (!enif_get_list_cell(env, tail, &head, &tail) || !enif_get_uint64(env, head, &m)) {
+      free(masks);
+      return enif_make_badarg(env);
+    }
+    masks[i] = m;
+  }
+  int rc = egm_routes_build(r->ctx, masks, n, self);
+  free(masks);
+  return rc ? error_tuple(env, r->ctx, rc) : ATOM_OK;
+}
+
+/* routes_delta(Ctx, Adds, Dels) -> {ok, Epoch} | {error, _}: the {FilterId,
+   NodeId} routes added and deleted since the last call (emqx_router:
+   do_add_route/2, do_delete_route/2) in one epoch; NET effects, as
+   subs_delta/3. */
+static ERL_NIF_TERM nif_routes_delta(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_res_t* r;
+  egm_sub_pair *add = NULL, *del = NULL;
+  unsigned na = 0, nd = 0;
+  if (argc != 3 || !get_ctx(env, argv[0], &r)) return enif_make_badarg(env);
+  if (!get_pairs(env, argv[1], &add, &na)) return enif_make_badarg(env);
+  if (!get_pairs(env, argv[2], &del, &nd)) {
+    free(add);
+    return enif_make_badarg(env);
+  }
+  uint64_t epoch = 0;
+  int rc = egm_routes_apply_delta(r->ctx, (const egm_route_pair*)add, na, (const egm_route_pair*)del, nd);
+  if (!rc) rc = egm_routes_commit(r->ctx, &epoch);
+  free(add);
+  free(del);
+  return rc ? error_tuple(env, r->ctx, rc) : enif_make_tuple2(env, ATOM_OK, enif_make_uint64(env, epoch));
+}
+
+/* routes_drop_node(Ctx, NodeId) -> {ok, [FilterId]} | {error, _}:
+   emqx_router_helper:cleanup_routes/1 for a node's atom dests; the filters
+   left without any route, ascending (the caller deletes them). */
+static ERL_NIF_TERM nif_routes_drop_node(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_res_t* r;
+  unsigned node;
+  if (argc != 2 || !get_ctx(env, argv[0], &r) || !enif_get_uint(env, argv[1], &node)) return enif_make_badarg(env);
+  uint32_t* ids = NULL;
+  uint64_t n = 0;
+  int rc = egm_routes_drop_node(r->ctx, node, &ids, &n);
+  if (rc) return error_tuple(env, r->ctx, rc);
+  ERL_NIF_TERM out = enif_make_list(env, 0);
+  for (uint64_t k = n; k-- > 0;) out = enif_make_list_cell(env, enif_make_uint(env, ids[k]), out);
+  if (ids) egm_result_free(ids);
+  return enif_make_tuple2(env, ATOM_OK, out);
+}
+
+/* forward(Ctx, [Topic]) -> {ok, [{NodeId, Pairs :: binary()}]} | {error, _}:
+   per remote node with any forward, its <<TopicIndex:32/native,
+   FilterId:32/native>> pairs in (topic, match order) — the payload of one
+   batched rpc to that node (emqx_broker:forward/4). */
+static ERL_NIF_TERM nif_forward(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+  egm_res_t* r;
+  uint8_t* blob;
+  uint32_t *off, n;
+  if (argc != 2 || !get_ctx(env, argv[0], &r) || !pack_list(env, argv[1], &blob, &off, &n))
+    return enif_make_badarg(env);
+  egm_result* res = NULL;
+  egm_forward* fw = NULL;
+  int rc = egm_match_batch(r->ctx, blob, off, n, EGM_MODE_ROUTES, &res);
+  free(blob);
+  free(off);
+  if (!rc) rc = egm_forward_batch(r->ctx, res, &fw);
+  if (res) egm_result_free(res);
+  if (rc) {
+    if (fw) egm_result_free(fw);
+    return error_tuple(env, r->ctx, rc);
+  }
+  ERL_NIF_TERM out = enif_make_list(env, 0);
+  for (uint32_t k = fw->n_nodes; k-- > 0;) {
+    const uint64_t lo = fw->node_row[k], hi = fw->node_row[k + 1];
+    if (hi == lo) continue;
+    ERL_NIF_TERM bin;
+    uint32_t* p = (uint32_t*)enif_make_new_binary(env, (size_t)(hi - lo) * 8, &bin);
+    if (!p) {
+      egm_result_free(fw);
+      return enif_make_badarg(env);
+    }
+    for (uint64_t j = lo; j < hi; ++j) {
+      p[2 * (j - lo)] = fw->topic[j];
+      p[2 * (j - lo) + 1] = fw->fid[j];
+    }
+    out = enif_make_list_cell(env, enif_make_tuple2(env, enif_make_uint(env, k), bin), out);
+  }
+  egm_result_free(fw);
+  return enif_make_tuple2(env, ATOM_OK, out);
+}
+
 /* ---- retained store ---- */
 static ERL_NIF_TERM rs_error(ErlNifEnv* env, egm_rstore* rs, int rc) {
   const char* msg = rs ? egm_rstore_last_error(rs) : "egm error";
@@ -779,6 +888,10 @@ static ErlNifFunc nif_funcs[] = {
     {"share_build", 2, nif_share_build, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"share_delta", 3, nif_share_delta, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     {"dispatch_batch", 5, nif_dispatch_batch, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"routes_build", 3, nif_routes_build, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"routes_delta", 3, nif_routes_delta, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"routes_drop_node", 2, nif_routes_drop_node, ERL_NIF_DIRTY_JOB_CPU_BOUND},
+    {"forward", 2, nif_forward, ERL_NIF_DIRTY_JOB_CPU_BOUND},
     /* the retained store: every call takes the store's lock, which a match or a
        delete holds across its device work, so none runs on a normal scheduler */
     {"rs_open", 1, nif_rs_open, ERL_NIF_DIRTY_JOB_CPU_BOUND},

@@ -42,6 +42,8 @@ EGM_GUARD_LOOP = 8
 NONE_ID = 0xFFFFFFFF
 GROUP_BIT = 0x80000000
 EGM_SUB_NONE = 0xFFFFFFFF   # a dispatched delivery slot with no receiver
+EGM_ROUTE_MAX_NODES = 64    # node ids of the route-node table (egm_routes_*)
+FWD_LOCAL = 0x80000000      # egm_forward's entry_fwd: the entry's filter has a local route
 
 # egm_dispatch_*'s member pick (EGM_PICK_*), by emqx_amd.broker.STRATEGIES' names
 EGM_PICK_RANDOM = 0
@@ -82,6 +84,16 @@ class egm_dispatch(C.Structure):
     _fields_ = [("n_topics", C.c_uint32), ("n_entries", C.c_uint64), ("n_deliveries", C.c_uint64),
                 ("row_ptr", _u64p), ("entry_pos", _u64p), ("sub", _u32p), ("entry_live", _u32p),
                 ("entry_shared", _u32p)]
+
+
+class egm_route_pair(C.Structure):
+    _fields_ = [("fid", C.c_uint32), ("node", C.c_uint32)]
+
+
+class egm_forward(C.Structure):
+    _fields_ = [("n_topics", C.c_uint32), ("n_nodes", C.c_uint32), ("n_entries", C.c_uint64),
+                ("n_forwards", C.c_uint64), ("node_row", _u64p), ("topic", _u32p), ("fid", _u32p),
+                ("entry_fwd", _u32p), ("topic_fwd", _u32p)]
 
 
 class egm_image_view(C.Structure):
@@ -152,6 +164,15 @@ SIGNATURES = {
                                      C.POINTER(C.POINTER(egm_dispatch))]),
     "egm_last_dispatch": (C.c_int, [_P, _u64p, _u64p, _u64p, _u64p]),
     "egm_get_dispatch_timing": (C.c_int, [_P, C.POINTER(C.c_double), _u64p]),
+    "egm_routes_build": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32]),
+    "egm_routes_apply_delta": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64]),
+    "egm_routes_commit": (C.c_int, [_P, _P]),
+    "egm_routes_last_commit": (C.c_int, [_P, _u64p, C.POINTER(C.c_int)]),
+    "egm_routes_drop_node": (C.c_int, [_P, C.c_uint32, C.POINTER(_u32p), _u64p]),
+    "egm_forward_device": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P, _P, C.c_uint64, _P, _P]),
+    "egm_forward_batch": (C.c_int, [_P, C.POINTER(egm_result), C.POINTER(C.POINTER(egm_forward))]),
+    "egm_last_forward": (C.c_int, [_P, _u64p, _u32p]),
+    "egm_get_forward_timing": (C.c_int, [_P, C.POINTER(C.c_double), _u64p]),
     "egm_shard_merge": (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, C.POINTER(_P), C.c_uint64, _P, _P, _P,
                                   C.c_uint64]),
     "egm_prefix_assign": (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P]),

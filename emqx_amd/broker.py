@@ -31,6 +31,15 @@ function of the caller's key alone — it returns exactly what the default path
 returns; random, round_robin and sticky pick by the device's own rules
 (include/emqx_gpu_match.h).
 
+``Broker(device_forward=True)`` takes the routes to other nodes from the GPU as
+well (egm_forward_batch over the route-node table, ``Router(device_routes=True)``):
+the ``("node", f, dst)`` deliveries, the ``forward`` entries, ``messages.forward``
+and "this filter has a local route" are read from the device's per-node lists
+and per-entry counts instead of a loop over every dest of every matched
+filter.  An entry's routes then come local first, the other nodes in node-id
+order (``aggre/1`` usorts them; the host loop keeps the order they were added
+in).  It combines with ``device_dispatch``.
+
 Subscriber sharding ({shard, Topic, I} bags beyond 1024 subscribers,
 emqx_broker.erl:149-157, emqx_broker_helper.erl:82-86) changes only the layout
 of the reference's ETS bags, never the delivery set; the fan-out CSR is the
@@ -136,10 +145,16 @@ class SharedSub:
 
 class Broker:
     def __init__(self, router: Optional[Router] = None, device: int = 0, node: str = "local",
-                 shared_strategy: str = "random", seed: int = 0, shards: int = 32, device_dispatch: bool = False):
+                 shared_strategy: str = "random", seed: int = 0, shards: int = 32, device_dispatch: bool = False,
+                 device_forward: bool = False):
         if shared_strategy not in STRATEGIES:
             raise ValueError(shared_strategy)
         self.router = router or Router(device=device, node=node)
+        # device_forward: the routes to other nodes from the GPU's route-node table (egm_forward_batch)
+        self.device_forward = device_forward
+        if device_forward:
+            self.router.device_routes = True
+        self.last_forward: Optional[dict] = None   # the last device forward pass (egm_forward_batch's arrays)
         self.node = node
         self.strategy = shared_strategy
         self.subscribers: Dict[bytes, List[int]] = {}            # filter -> local sub ids
@@ -382,6 +397,7 @@ class Broker:
         from . import _lib as L
         r = self.router
         res, drow, dfid, raw, d = self._dispatch(topics, clientids, liveness=False)
+        fw = self._forwards(res)
         sub = d["sub"]
         out = []
         for k in range(len(topics)):
@@ -396,10 +412,11 @@ class Broker:
                     dl.append(("group", f, self.group_names[e & ~GROUP_BIT], s))
                 else:
                     dl.append(("sub", f, s))
-            for fid in res.row(k).tolist():
+            for i in range(int(res.row_ptr[k]), int(res.row_ptr[k + 1])):
+                fid = int(res.ids[i])
                 f = r.filter_of(fid)
-                for dst in r.routes[f]:
-                    if dst != self.node and not (isinstance(dst, tuple) and dst[0] == "group"):
+                for dst in self._node_routes(fw, k, i, fid, f):
+                    if dst != self.node:
                         dl.append(("node", f, dst))
             out.append(dl)
         return out
@@ -408,6 +425,7 @@ class Broker:
         from . import _lib as L
         r = self.router
         res, drow, dfid, raw, d = self._dispatch(topics, clientids, liveness=True)
+        fw = self._forwards(res)
         sub, live, shared, epos = d["sub"], d["entry_live"], d["entry_shared"], d["entry_pos"]
         out = []
         for k, t in enumerate(topics):
@@ -428,9 +446,7 @@ class Broker:
                 # entry_shared against the group routes of the filter
                 assert sum(1 for x in r.routes[f] if isinstance(x, tuple) and x[0] == "group") == n_groups
                 assert sum(1 for (ff, _), ok in served.items() if ff == f and ok) == int(shared[i])
-                for dst in r.routes[f]:
-                    if isinstance(dst, tuple) and dst[0] == "group":
-                        continue
+                for dst in self._node_routes(fw, k, i, fid, f):
                     if dst == self.node:
                         n = int(live[i])
                         if n:
@@ -447,6 +463,31 @@ class Broker:
                 self._dropped(t, sysf)
             out.append(entries)
         return out
+
+    def _forwards(self, res):
+        """With device_forward: egm_forward_batch over the match result — the
+        remote dests of each (row, filter id), read from the per-node lists —
+        else None (the host loop over the routes)."""
+        if not self.device_forward:
+            return None
+        r = self.router
+        r.commit()
+        f = self.last_forward = r.m.forward(res)
+        dests: Dict[Tuple[int, int], list] = {}
+        nrow, topic, fid = f["node_row"], f["topic"], f["fid"]
+        for nid, name in enumerate(r.node_names):
+            for j in range(int(nrow[nid]), int(nrow[nid + 1])):
+                dests.setdefault((int(topic[j]), int(fid[j])), []).append(name)
+        return dests, f["entry_fwd"], f["topic_fwd"]
+
+    def _node_routes(self, fw, k: int, i: int, fid: int, f: bytes):
+        """The node dests (not the {Group, Node} ones) of match entry i — filter
+        id `fid` of row k: the host's route list, or the device's answer."""
+        if fw is None:
+            return [d for d in self.router.routes[f] if Router.is_node(d)]
+        dests, entry_fwd, _ = fw
+        local = [self.node] if int(entry_fwd[i]) & 0x80000000 else []
+        return local + dests.get((k, fid), [])
 
     def _apply_ordered(self, add, dele):
         """One delta for the pairs touched since the last publish: each pair's
@@ -488,6 +529,7 @@ class Broker:
         r = self.router
         res = r.match_filters_batch(topics)
         drow, dfid, dsub = r.m.fanout(res)
+        fw = self._forwards(res)
         out = []
         for k, t in enumerate(topics):
             dl: List[tuple] = []
@@ -502,10 +544,11 @@ class Broker:
                 else:
                     dl.append(("sub", f, s))
             # routes to other nodes are forwarded, not expanded here
-            for fid in res.row(k).tolist():
+            for i in range(int(res.row_ptr[k]), int(res.row_ptr[k + 1])):
+                fid = int(res.ids[i])
                 f = r.filter_of(fid)
-                for d in r.routes[f]:
-                    if d != self.node and not (isinstance(d, tuple) and d[0] == "group"):
+                for d in self._node_routes(fw, k, i, fid, f):
+                    if d != self.node:
                         dl.append(("node", f, d))
             out.append(dl)
         return out
@@ -531,6 +574,7 @@ class Broker:
         r = self.router
         res = r.match_filters_batch(topics)
         drow, dfid, dsub = r.m.fanout(res)
+        fw = self._forwards(res)
         out = []
         for k, t in enumerate(topics):
             sysf = bool(sys_flags[k]) if sys_flags else False
@@ -544,12 +588,12 @@ class Broker:
                     alive[f] = alive.get(f, 0) + 1
             entries: List[tuple] = []
             groups = set()
-            for fid in res.row(k).tolist():
+            for i in range(int(res.row_ptr[k]), int(res.row_ptr[k + 1])):
+                fid = int(res.ids[i])
                 f = r.filter_of(fid)
-                for d in r.routes[f]:
-                    if isinstance(d, tuple) and d[0] == "group":
-                        groups.add((f, d[1]))
-                    elif d == self.node:
+                groups.update((f, d[1]) for d in r.routes[f] if not Router.is_node(d))
+                for d in self._node_routes(fw, k, i, fid, f):
+                    if d == self.node:
                         n = alive.get(fid, 0)
                         if n:
                             entries.append((d, f, ("ok", n)))

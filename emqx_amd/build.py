@@ -25,10 +25,10 @@ SYNTH = os.path.join(HERE, "libegm_synth.so")
 ORACLE = os.path.join(ROOT, "oracle", "liboracle_trie.so")
 
 # the library's sources (tools/build_variant.py builds the same lists)
-HIP_SOURCES = ("egm_kernels.hip", "egm_pack.hip")
+HIP_SOURCES = ("egm_kernels.hip", "egm_pack.hip", "egm_route.hip")
 HOST_SOURCES = ("egm_table.cpp", "egm_bulk.cpp", "egm_capi.cpp", "egm_match.cpp", "egm_pipe.cpp", "egm_fanout.cpp",
-                "egm_dispatch.cpp", "egm_part.cpp", "egm_retain.cpp", "egm_dma.cpp")
-HEADERS = [os.path.join(CSRC, f) for f in ("egm_common.h", "egm_table.h", "egm_kernels.h", "egm_dma.h", "egm_pack.h",
+                "egm_dispatch.cpp", "egm_route.cpp", "egm_part.cpp", "egm_retain.cpp", "egm_dma.cpp")
+HEADERS = [os.path.join(CSRC, f) for f in ("egm_common.h", "egm_table.h", "egm_kernels.h", "egm_dma.h", "egm_pack.h", "egm_route.h",
                                            "egm_alloc.h", "egm_buf.h", "egm_ctx.h")] + [
     os.path.join(ROOT, "include", "emqx_gpu_match.h")]
 
@@ -60,7 +60,7 @@ def build_lib(verbose=False, force=False) -> str:
     objs = []
     for name in HIP_SOURCES:
         hip_src = os.path.join(CSRC, name)
-        o = os.path.join(BUILD, name.replace(".hip", ".o"))
+        o = os.path.join(BUILD, name + ".o")   # egm_route.hip beside egm_route.cpp: the suffix stays in the name
         if force or _stale(o, [hip_src] + HEADERS):
             _run([_hipcc(), f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-result",
                   "-Wno-unused-value", "-c", hip_src, "-o", o], verbose)

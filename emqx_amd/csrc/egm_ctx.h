@@ -6,6 +6,7 @@
 //   egm_pipe.cpp    the host pipeline (egm_match_submit / _wait / _batch)
 //   egm_fanout.cpp  the subscriber table and the fan-out
 //   egm_dispatch.cpp the dead bitmap, the share table and the dispatch
+//   egm_route.cpp   the route-node table and the forward pass
 //   egm_part.cpp    shard merge, prefix partition, the host-only image API
 // Everything here is internal to the library (hidden visibility).
 #pragma once
@@ -26,6 +27,7 @@
 #include "egm_alloc.h"
 #include "egm_buf.h"
 #include "egm_kernels.h"
+#include "egm_route.h"
 #include "egm_table.h"
 
 #pragma GCC visibility push(hidden)
@@ -188,7 +190,7 @@ struct Timing {
     uint64_t n = 0;
   };
   bool on = false;
-  Series walk, fan, disp;   // disp: the dispatch's resolve pass alone
+  Series walk, fan, disp, fwd;   // disp: the dispatch's resolve pass alone; fwd: the forward pass
   std::vector<hipEvent_t> ev_free;
   hipEvent_t take_event() {
     if (!ev_free.empty()) {
@@ -228,6 +230,7 @@ struct Timing {
     drain(walk);
     drain(fan);
     drain(disp);
+    drain(fwd);
   }
 };
 
@@ -268,6 +271,35 @@ struct DispState {
   // the last dispatch (egm_last_dispatch)
   DevBuf stats, mkey, epos, elive, eshared;
   uint64_t seq = 0;                  // dispatches launched: the random pick's sequence number
+  hipStream_t last_stream = nullptr;
+  bool launched = false;
+};
+
+// Cluster routes (egm_route.cpp): the route-node table — the emqx_route bag
+// restricted to atom dests (emqx_router.erl:114-125), one 64-bit node mask per
+// filter id — and the forward pass's workspaces.  The host mirror is
+// authoritative; a commit patches the changed masks into the device copy no
+// forward pass in flight reads and makes it current (the subscriber commit's
+// two-copy scheme).  A node drop rewrites one copy in a streaming pass; the
+// other copy gets the same pass when it next becomes the commit's target.
+struct RouteState {
+  bool built = false;
+  uint32_t self_node = 0;
+  uint32_t n_nodes = 0;                 // largest node id ever set + 1
+  uint32_t n_fid_slots = 0;             // masks of each device copy
+  std::vector<uint64_t> mask;           // host mirror (longer than the device copies until a commit uploads it)
+  std::vector<uint32_t> pending;        // filter ids changed since the last commit
+  std::vector<uint32_t> stale[2];       // masks a copy lacks (changed since it was written)
+  std::vector<uint32_t> drops[2];       // node drops a copy lacks
+  DevBuf copy[2];
+  int cur = 0;                          // the copy the forward pass reads
+  StreamUses uses[2];                   // the queued forward passes that read each copy
+  uint64_t epoch = 0, last_patched = 0;
+  bool last_rebuilt = false;
+  DevBuf drop_out, drop_n;              // egm_routes_drop_node's emptied list
+  // the forward pass
+  DevBuf tile_cnt, tile_base, tile_sums, state;
+  DevBuf mrow, mids, nrow, ftopic, ffid, efwd, tfwd;   // egm_forward_batch
   hipStream_t last_stream = nullptr;
   bool launched = false;
 };
@@ -356,6 +388,7 @@ struct egm_ctx {
   egm::PartState part;   // shard merge and prefix partition routing (egm_part.cpp)
   egm::FanState fan;     // subscriber table and fan-out (egm_fanout.cpp)
   egm::DispState disp;   // dead bitmap, share table and dispatch (egm_dispatch.cpp)
+  egm::RouteState route; // route-node table and forward pass (egm_route.cpp)
   egm::Timing timing;
 
   // The per-context workspaces (fan-out, merge, routes) are shared by every

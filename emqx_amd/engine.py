@@ -456,6 +456,85 @@ class GpuMatcher:
         self._check(self.lib.egm_get_dispatch_timing(self.ctx, C.byref(ms), C.byref(k)), "egm_get_dispatch_timing")
         return {"resolve_ms": ms.value, "resolve_launches": k.value}
 
+    # -- cluster routes on the device -------------------------------------------
+    @staticmethod
+    def _pairs(rows) -> np.ndarray:
+        return np.ascontiguousarray(np.asarray(rows, dtype=np.uint32).reshape(-1, 2))
+
+    def routes_build(self, masks, self_node: int = 0):
+        """egm_routes_build: the route-node table from one u64 node mask per filter id."""
+        a = np.ascontiguousarray(masks, dtype=np.uint64)
+        self._check(self.lib.egm_routes_build(self.ctx, _ptr(a) if len(a) else None, len(a), self_node),
+                    "egm_routes_build")
+
+    def routes_apply_delta(self, add=(), delete=()):
+        """egm_routes_apply_delta: (filter id, node id) pairs to add / remove (net changes)."""
+        a, d = self._pairs(add), self._pairs(delete)
+        self._check(self.lib.egm_routes_apply_delta(self.ctx, _ptr(a) if len(a) else None, len(a),
+                                                    _ptr(d) if len(d) else None, len(d)), "egm_routes_apply_delta")
+
+    def routes_commit(self) -> int:
+        ep = C.c_uint64()
+        self._check(self.lib.egm_routes_commit(self.ctx, C.byref(ep)), "egm_routes_commit")
+        return ep.value
+
+    def routes_last_commit(self) -> dict:
+        p, r = C.c_uint64(), C.c_int()
+        self._check(self.lib.egm_routes_last_commit(self.ctx, C.byref(p), C.byref(r)), "egm_routes_last_commit")
+        return {"patched": p.value, "rebuilt": bool(r.value)}
+
+    def routes_drop_node(self, node: int) -> np.ndarray:
+        """egm_routes_drop_node: every route to `node` goes; the filter ids left without a route, ascending."""
+        out, n = L._u32p(), C.c_uint64()
+        self._check(self.lib.egm_routes_drop_node(self.ctx, node, C.byref(out), C.byref(n)), "egm_routes_drop_node")
+        try:
+            return np.ctypeslib.as_array(out, shape=(n.value,)).copy() if n.value else np.zeros(0, np.uint32)
+        finally:
+            if out:
+                self.lib.egm_result_free(out)
+
+    def forward_device(self, d_mrow: int, d_mids: int, mids_len: int, n: int, stream: int, d_node_row: int,
+                       d_fwd_topic: int, d_fwd_fid: int, cap: int, d_entry_fwd: int = 0, d_topic_fwd: int = 0):
+        """egm_forward_device: per remote node the (row, filter) pairs of a device match CSR (raw device pointers)."""
+        self._check(self.lib.egm_forward_device(self.ctx, d_mrow, d_mids, mids_len, n, stream or None, d_node_row,
+                                                d_fwd_topic, d_fwd_fid, cap, d_entry_fwd or None,
+                                                d_topic_fwd or None), "egm_forward_device")
+
+    def forward(self, m: MatchResult) -> dict:
+        """egm_forward_batch: the forwards of a host match result — node_row u64[65],
+        topic / fid u32 (node k's pairs are [node_row[k], node_row[k+1])), entry_fwd
+        u32[n_ids] (remote nodes, L.FWD_LOCAL: a local route), topic_fwd u32[n]."""
+        n = len(m.row_ptr) - 1
+        counts = np.diff(m.row_ptr).astype(np.uint32)
+        r = L.egm_result(n, len(m.ids), counts.ctypes.data_as(L._u32p),
+                         m.row_ptr.ctypes.data_as(L._u64p), m.ids.ctypes.data_as(L._u32p),
+                         m.flags.ctypes.data_as(L._u8p), m.epoch, m.visited, m.n_heavy, m.n_error)
+        out = C.POINTER(L.egm_forward)()
+        self._check(self.lib.egm_forward_batch(self.ctx, C.byref(r), C.byref(out)), "egm_forward_batch")
+        try:
+            f = out.contents
+            tot, ne = int(f.n_forwards), int(f.n_entries)
+
+            def arr(p, k, dt):
+                return np.ctypeslib.as_array(p, shape=(k,)).copy() if k else np.zeros(0, dt)
+
+            return {"node_row": arr(f.node_row, int(f.n_nodes) + 1, np.uint64), "topic": arr(f.topic, tot, np.uint32),
+                    "fid": arr(f.fid, tot, np.uint32), "entry_fwd": arr(f.entry_fwd, ne, np.uint32),
+                    "topic_fwd": arr(f.topic_fwd, n, np.uint32)}
+        finally:
+            self.lib.egm_result_free(out)
+
+    def last_forward(self) -> dict:
+        """Total of the last forward pass and whether its lists were too small (synchronises it)."""
+        tot, ovf = C.c_uint64(), C.c_uint32()
+        self._check(self.lib.egm_last_forward(self.ctx, C.byref(tot), C.byref(ovf)), "egm_last_forward")
+        return {"forwards": tot.value, "overflow": ovf.value}
+
+    def forward_timing(self) -> dict:
+        ms, k = C.c_double(), C.c_uint64()
+        self._check(self.lib.egm_get_forward_timing(self.ctx, C.byref(ms), C.byref(k)), "egm_get_forward_timing")
+        return {"forward_ms": ms.value, "forward_launches": k.value}
+
     # -- multi-GPU filter shards --------------------------------------------------
     def shard_merge(self, n_shards: int, n: int, d_counts: int, d_shard_ids: Sequence[int], total: int,
                     stream: int, d_row: int, d_ids: int, ids_cap: int):

@@ -10,6 +10,12 @@ expands each matched filter to its destinations.
 Route add/delete keep the reference's rules: a route is added once
 (:116-117); a filter enters the table with its first route and leaves with its
 last (:230-248).
+
+``Router(device_routes=True)`` also keeps the route-node table on the GPU
+(egm_routes_*): every dest that is a node (not a ``("group", G)`` tuple) gets a
+small node id on first sight, the (filter id, node id) changes since the last
+commit are published with the table commit, and ``cleanup_routes(node)``
+(emqx_router_helper.erl:137-146) drops a node's routes in one device pass.
 """
 from __future__ import annotations
 
@@ -30,7 +36,8 @@ def _check_bin(x):
 
 
 class Router:
-    def __init__(self, matcher: Optional[GpuMatcher] = None, device: int = 0, node: str = "local"):
+    def __init__(self, matcher: Optional[GpuMatcher] = None, device: int = 0, node: str = "local",
+                 device_routes: bool = False):
         self.m = matcher or GpuMatcher(device)
         self.node = node
         self.routes: Dict[bytes, List[object]] = {}
@@ -38,6 +45,47 @@ class Router:
         self._names: Dict[int, bytes] = {}
         self._next = 0
         self._dirty = False
+        # the route-node table on the GPU (egm_routes_*): built at the first commit, then kept by deltas
+        self.device_routes = device_routes
+        self.node_ids: Dict[object, int] = {node: 0}
+        self.node_names: List[object] = [node]
+        self._r_built = False
+        self._r_touched: Dict[tuple, None] = {}   # (filter id, node id) pairs changed since the last commit
+
+    @staticmethod
+    def is_node(dest) -> bool:
+        """An atom dest of emqx_route (a node), not a {Group, Node} one."""
+        return not (isinstance(dest, tuple) and len(dest) == 2 and dest[0] == "group")
+
+    def node_id(self, dest) -> int:
+        """The node id of a dest in the route-node table, assigned on first sight."""
+        nid = self.node_ids.get(dest)
+        if nid is None:
+            if len(self.node_names) >= L.EGM_ROUTE_MAX_NODES:
+                raise ValueError("more than EGM_ROUTE_MAX_NODES nodes")
+            nid = self.node_ids[dest] = len(self.node_names)
+            self.node_names.append(dest)
+        return nid
+
+    def _route_mask(self, fid: int) -> int:
+        f = self._names.get(fid)
+        return sum(1 << self.node_id(d) for d in self.routes.get(f, ()) if self.is_node(d)) if f is not None else 0
+
+    def _commit_routes(self):
+        if not self._r_built:
+            import numpy as np
+            masks = np.zeros(self._next, dtype=np.uint64)
+            for fid in self._names:
+                masks[fid] = self._route_mask(fid)
+            self.m.routes_build(masks, 0)
+            self._r_built = True
+        elif self._r_touched:
+            # each touched pair's net effect, read from the host lists
+            add = [p for p in self._r_touched if self._route_mask(p[0]) >> p[1] & 1]
+            dele = [p for p in self._r_touched if not self._route_mask(p[0]) >> p[1] & 1]
+            self.m.routes_apply_delta(add=add, delete=dele)
+            self.m.routes_commit()
+        self._r_touched.clear()
 
     # -- table maintenance (emqx_router.erl:114-125,164-170,227-248) ----------
     def add_route(self, topic: bytes, dest=None) -> str:
@@ -57,6 +105,8 @@ class Router:
             self._names[fid] = topic
             self._dirty = True
         cur.append(dest)
+        if self._r_built and self.is_node(dest):
+            self._r_touched[(self._ids[topic], self.node_id(dest))] = None
         return "ok"
 
     def delete_route(self, topic: bytes, dest=None) -> str:
@@ -69,6 +119,8 @@ class Router:
         if not cur or dest not in cur:
             return "ok"
         cur.remove(dest)
+        if self._r_built and self.is_node(dest):
+            self._r_touched[(self._ids[topic], self.node_id(dest))] = None
         if not cur:
             del self.routes[topic]
             fid = self._ids.pop(topic)
@@ -81,6 +133,32 @@ class Router:
         if self._dirty:
             self.m.commit()
             self._dirty = False
+        if self.device_routes:
+            self._commit_routes()
+
+    def cleanup_routes(self, node) -> List[bytes]:
+        """cleanup_routes/1 (emqx_router_helper.erl:137-146, 175-179) for the
+        atom-dest pattern: every route to `node` goes; the filters left without
+        a route leave the table and are returned.  With ``device_routes`` the
+        device drops the node's bit in one pass (egm_routes_drop_node) and says
+        which filters it emptied."""
+        hit = [t for t, ds in self.routes.items() if node in ds]
+        if self.device_routes:
+            self.commit()   # (assigns the ids of the nodes routed to)
+        if self.device_routes and node in self.node_ids:
+            emptied = self.m.routes_drop_node(self.node_ids[node]).tolist()
+            # (a filter that keeps only {Group, Node} routes has no node left, and stays in the table)
+            want = sorted(self._ids[t] for t in hit if not any(self.is_node(d) and d != node for d in self.routes[t]))
+            if emptied != want:
+                raise RuntimeError("cleanup_routes: the device's emptied filters differ from the host's")
+        gone = []
+        for topic in hit:
+            key = (self._ids[topic], self.node_ids.get(node))
+            self.do_delete_route(topic, node)
+            self._r_touched.pop(key, None)   # the device pass has done it
+            if topic not in self.routes:
+                gone.append(topic)
+        return gone
 
     # -- lookups ----------------------------------------------------------------
     def lookup_routes(self, topic: bytes) -> List[Route]:

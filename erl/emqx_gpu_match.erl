@@ -21,6 +21,8 @@
          subs_delta/3, publish_batch/2]).
 %% dispatch on the device: liveness, $share member pick, route counts
 -export([subs_set_dead/3, share_build/2, share_delta/3, dispatch_batch/5]).
+%% cluster routes on the device: node sets per filter, forwards by node
+-export([routes_build/3, routes_delta/3, routes_drop_node/2, forward/2, filter_id/1]).
 %% the retained store (emqx_retainer_mnesia's table mirrored on the device)
 -export([rs_open/1, rs_put/4, rs_delete/2, rs_delete_matching/2, rs_set_max_retained/2, rs_clean/1, rs_size/1, rs_commit/1,
          rs_clear_expired/2, rs_match/4]).
@@ -61,6 +63,18 @@ subs_set_dead(_Ctx, _Subs, _Dead) -> erlang:nif_error(nif_not_loaded).
 share_build(_Ctx, _Members) -> erlang:nif_error(nif_not_loaded).
 share_delta(_Ctx, _Adds, _Dels) -> erlang:nif_error(nif_not_loaded).
 dispatch_batch(_Ctx, _Topics, _Keys, _Strategy, _Seed) -> erlang:nif_error(nif_not_loaded).
+%% Cluster routes (emqx_broker:do_route/2's forward arm, emqx_broker.erl:242-247;
+%% the emqx_route bag's atom dests, emqx_router.erl:114-125): routes_build/3 takes
+%% one 64-bit node mask per filter id and the local node's id; routes_delta/3 the
+%% {FilterId, NodeId} routes added and deleted since the last call (net effects),
+%% -> {ok, Epoch}; routes_drop_node/2 is emqx_router_helper:cleanup_routes/1 for a
+%% node's atom dests, -> {ok, [FilterId]} the filters left without a route;
+%% forward/2 -> {ok, [{NodeId, <<TopicIndex:32/native, FilterId:32/native, ...>>}]},
+%% per remote node the payload of one batched rpc.  Node ids are 0..63.
+routes_build(_Ctx, _Masks, _SelfNode) -> erlang:nif_error(nif_not_loaded).
+routes_delta(_Ctx, _Adds, _Dels) -> erlang:nif_error(nif_not_loaded).
+routes_drop_node(_Ctx, _Node) -> erlang:nif_error(nif_not_loaded).
+forward(_Ctx, _Topics) -> erlang:nif_error(nif_not_loaded).
 %% Retained store: topic -> {MsgId, ExpiryMs}; the messages stay with the caller.
 %% rs_put/4 -> ok | {error, full}; rs_delete_matching/2 and rs_clear_expired/2
 %% -> {ok, [MsgId]} (the dropped ids); rs_match/4 -> {ok, [[MsgId]]} per filter,
@@ -91,6 +105,13 @@ ctx() -> persistent_term:get(?MODULE).
 
 %% Filter binary of a filter id (ids are assigned by build/1 and sync/2).
 filter_of(Id) -> ets:lookup_element(?TAB, Id, 2).
+
+%% Filter id of a filter in the table, or undefined.
+filter_id(F) ->
+    case ets:lookup(?TAB, {filter, F}) of
+        [{_, Id}] -> Id;
+        [] -> undefined
+    end.
 
 %% Filter binaries of matched ids; an id deleted since its batch was matched
 %% is skipped (its filter has no routes left; ids are never reused).

@@ -19,6 +19,16 @@
 %% insert_trie_route / delete_trie_route, evaluated after the commit, so the
 %% final state never depends on event interleaving.
 %%
+%% Cluster routes.  A route event's Dest is kept: for an atom Dest other than
+%% node() the {Topic, Dest} pair is staged, the node gets a small id on first
+%% sight (0 is node(); at most 64 nodes, emqx_gpu_match:routes_delta/3), and a
+%% flush publishes each staged pair's net effect — the pair is in the device's
+%% route-node table iff emqx_router:lookup_routes/1 holds it at flush time —
+%% after the epoch that holds its filter.  {membership, {mnesia, down, Node}}
+%% (emqx_router_helper.erl:137-146 cleanup_routes/1) drops the node's routes in
+%% one device pass.  {Group, Node} dests are not tracked: the subscriber and
+%% share tables carry no node.
+%%
 %% Simple table events carry the record tagged with the TABLE name
 %% ({write, {emqx_route, Topic, Dest}, ActivityId}), not with its record name
 %% `route` (emqx_router.erl:78-81 creates emqx_route with {record_name, route};
@@ -64,7 +74,9 @@
 
 -define(PENDING, emqx_gpu_pending).
 
--record(st, {touched = #{}, n = 0, size, linger, timer}).
+-record(st, {touched = #{}, n = 0, size, linger, timer,
+             nodes = #{},    %% Node -> node id in the route-node table
+             pairs = #{}}).  %% {Topic, Node} routes touched since the last flush
 
 start_link(Opts) when is_map(Opts) ->
     gen_server:start_link({local, ?MODULE}, ?MODULE, Opts, []).
@@ -108,8 +120,35 @@ init(Opts) ->
     _ = ets:new(?PENDING, [named_table, public, set, {read_concurrency, true}, {write_concurrency, true}]),
     {ok, _} = mnesia:subscribe({table, ?ROUTE_TAB, simple}),
     %% initial image: every wildcard filter with a route (emqx_trie's content)
-    ok = emqx_gpu_match:build([T || T <- emqx_router:topics(), emqx_topic:wildcard(T)]),
-    {ok, #st{size = maps:get(batch_size, Opts, 65536), linger = maps:get(linger_ms, Opts, 5)}}.
+    Filters = [T || T <- emqx_router:topics(), emqx_topic:wildcard(T)],
+    ok = emqx_gpu_match:build(Filters),
+    %% a node going down: mnesia's own event here; ekka's {membership, {mnesia, down, Node}}
+    %% reaches this process once the integration registers it (INTEGRATION.md §2)
+    {ok, _} = mnesia:subscribe(system),
+    %% the route-node table: every atom dest of those filters (ids follow build/1's order)
+    {RevMasks, Nodes} = lists:foldl(
+                          fun(T, {Acc, Ns0}) ->
+                                  {Mask, Ns2} = lists:foldl(fun(D, {M, Ns}) ->
+                                                                    {Id, Ns1} = node_id(D, Ns),
+                                                                    {M bor (1 bsl Id), Ns1}
+                                                            end, {0, Ns0}, node_dests(T)),
+                                  {[Mask | Acc], Ns2}
+                          end, {[], #{node() => 0}}, Filters),
+    ok = emqx_gpu_match:routes_build(emqx_gpu_match:ctx(), lists:reverse(RevMasks), 0),
+    {ok, #st{size = maps:get(batch_size, Opts, 65536), linger = maps:get(linger_ms, Opts, 5), nodes = Nodes}}.
+
+%% The atom dests of a topic's routes (emqx_router:lookup_routes/1 -> [#route{}]).
+node_dests(T) ->
+    [D || {route, _, D} <- emqx_router:lookup_routes(T), is_atom(D)].
+
+node_id(Node, Nodes) ->
+    case maps:get(Node, Nodes, undefined) of
+        undefined ->
+            Id = maps:size(Nodes),
+            true = Id < 64,   %% EGM_ROUTE_MAX_NODES
+            {Id, Nodes#{Node => Id}};
+        Id -> {Id, Nodes}
+    end.
 
 handle_call(flush, _From, St) ->
     {reply, ok, publish(St)};
@@ -119,9 +158,14 @@ handle_call(_Req, _From, St) ->
 handle_cast(_Msg, St) ->
     {noreply, St}.
 
-handle_info({mnesia_table_event, {write, {?ROUTE_TAB, T, _Dest}, _}}, St) -> {noreply, touch(T, St)};
-handle_info({mnesia_table_event, {delete_object, {?ROUTE_TAB, T, _Dest}, _}}, St) -> {noreply, touch(T, St)};
-handle_info({mnesia_table_event, {delete, {?ROUTE_TAB, T}, _}}, St) -> {noreply, touch(T, St)};
+handle_info({mnesia_table_event, {write, {?ROUTE_TAB, T, Dest}, _}}, St) -> {noreply, touch(T, stage(T, Dest, St))};
+handle_info({mnesia_table_event, {delete_object, {?ROUTE_TAB, T, Dest}, _}}, St) ->
+    {noreply, touch(T, stage(T, Dest, St))};
+handle_info({mnesia_table_event, {delete, {?ROUTE_TAB, T}, _}}, St = #st{nodes = Nodes}) ->
+    %% every route of T went: each known node's pair is re-read at the flush
+    {noreply, touch(T, lists:foldl(fun(N, S) -> stage(T, N, S) end, St, maps:keys(Nodes)))};
+handle_info({membership, {mnesia, down, Node}}, St) -> {noreply, node_down(Node, St)};
+handle_info({mnesia_system_event, {mnesia_down, Node}}, St) -> {noreply, node_down(Node, St)};
 handle_info(linger, St) ->
     {noreply, publish(St#st{timer = undefined})};
 handle_info(_Info, St) ->
@@ -130,6 +174,28 @@ handle_info(_Info, St) ->
 terminate(_Reason, St) ->
     _ = publish(St),
     ok.
+
+%% cleanup_routes/1 (emqx_router_helper.erl:137-146) on the device; the emptied
+%% filters leave the filter table through their own delete events.
+node_down(Node, St0 = #st{nodes = Nodes}) ->
+    St = publish(St0),   %% the staged pairs first: the drop then sees them
+    case maps:get(Node, Nodes, undefined) of
+        undefined -> St;
+        Id ->
+            {ok, _Emptied} = emqx_gpu_match:routes_drop_node(emqx_gpu_match:ctx(), Id),
+            St
+    end.
+
+%% An atom dest other than node(): the pair is staged under the node's id.
+stage(T, Dest, St = #st{nodes = Nodes, pairs = P}) when is_atom(Dest), Dest =/= node() ->
+    case emqx_topic:wildcard(T) of
+        true ->
+            {_Id, Nodes1} = node_id(Dest, Nodes),
+            St#st{nodes = Nodes1, pairs = P#{{T, Dest} => true}};
+        false -> St
+    end;
+stage(_T, _Dest, St) ->
+    St.
 
 touch(T, St = #st{touched = M, n = N, size = Size, linger = Ms, timer = Tm}) ->
     case emqx_topic:wildcard(T) andalso not maps:is_key(T, M) of
@@ -145,12 +211,20 @@ touch(T, St = #st{touched = M, n = N, size = Size, linger = Ms, timer = Tm}) ->
 
 publish(St = #st{n = 0}) ->
     St;
-publish(St = #st{touched = M, timer = Tm}) ->
+publish(St = #st{touched = M, timer = Tm, nodes = Nodes, pairs = P}) ->
     _ = Tm =:= undefined orelse erlang:cancel_timer(Tm),
     Touched = maps:keys(M),
+    %% the staged route pairs' net effect; a filter about to leave still has its id here
+    {Held, Gone} = lists:partition(fun({T, N}) -> lists:member(N, node_dests(T)) end, maps:keys(P)),
+    Dels = [{Id, maps:get(N, Nodes)} || {T, N} <- Gone, (Id = emqx_gpu_match:filter_id(T)) =/= undefined],
     Snap = [{T, ets:lookup(?PENDING, T)} || T <- Touched],   %% before has_routes/1
     {Ins, Del} = lists:partition(fun emqx_router:has_routes/1, Touched),
     ok = emqx_gpu_match:sync(Ins, Del),   %% returns after the epoch holding Ins is published
+    Adds = [{Id, maps:get(N, Nodes)} || {T, N} <- Held, (Id = emqx_gpu_match:filter_id(T)) =/= undefined],
+    case Adds =:= [] andalso Dels =:= [] of
+        true -> ok;
+        false -> {ok, _} = emqx_gpu_match:routes_delta(emqx_gpu_match:ctx(), Adds, Dels)
+    end,
     InsSet = maps:from_list([{T, true} || T <- Ins]),
     lists:foreach(
       fun({T, Objs}) ->
@@ -159,4 +233,4 @@ publish(St = #st{touched = M, timer = Tm}) ->
                   false -> [ets:delete_object(?PENDING, O) || O = {_, _, done} <- Objs]
               end
       end, Snap),
-    St#st{touched = #{}, n = 0, timer = undefined}.
+    St#st{touched = #{}, n = 0, timer = undefined, pairs = #{}}.

@@ -447,6 +447,93 @@ int egm_last_dispatch(egm_ctx* ctx, uint64_t* dead_dropped, uint64_t* groups_res
    egm_set_timing (the fan-out before it is counted in egm_get_timing). */
 int egm_get_dispatch_timing(egm_ctx* ctx, double* resolve_ms, uint64_t* launches);
 
+/* ---- cluster routes on the device: node sets per filter, forwards by node ----
+   The third arm of emqx_broker:do_route/2 (apps/emqx/src/emqx_broker.erl:
+   242-247): forward(Node, To, Delivery, _) for a route whose dest is another
+   node (:244-245, 262-280).  The route-node table is the emqx_route bag
+   restricted to atom dests (apps/emqx/src/emqx_router.erl:114-125, 164-170,
+   230-248): one 64-bit mask per filter id, bit n set when a route
+   {filter, node n} exists.  Node ids are small integers the caller assigns,
+   0 .. EGM_ROUTE_MAX_NODES - 1; a larger id is EGM_E_INVAL.  The local
+   node's bit is kept too, so a reader knows whether a local route exists; a
+   filter id at or past the table's slots has mask 0. */
+#define EGM_ROUTE_MAX_NODES 64
+typedef struct egm_route_pair {
+  uint32_t fid;    /* filter id */
+  uint32_t node;   /* node id, < EGM_ROUTE_MAX_NODES */
+} egm_route_pair;
+/* <- the table as a whole (emqx_router.erl:114-125 over every route):
+   masks[n_fid_slots] indexed by filter id, self_node the local node's id.
+   Replaces the table and publishes it; a quarter + 4096 spare slots are
+   reserved, so filters added later are patched in. */
+int egm_routes_build(egm_ctx* ctx, const uint64_t* masks, uint32_t n_fid_slots, uint32_t self_node);
+/* <- do_add_route/2, do_delete_route/2 (emqx_router.erl:114-125, 164-170,
+   230-248).  egm_subs_apply_delta's contract: NET changes, a pair in both
+   lists is EGM_E_INVAL and nothing is applied, adding a present pair or
+   removing an absent one does nothing.  An added filter id must be below
+   max(the table's slots, the match table's filter-id range) + 2^22.
+   EGM_E_STATE before egm_routes_build. */
+int egm_routes_apply_delta(egm_ctx* ctx, const egm_route_pair* add, uint64_t n_add, const egm_route_pair* del,
+                           uint64_t n_del);
+/* Publishes the staged changes in one epoch, by the subscriber commit's
+   scheme: the changed masks are patched into the device copy no forward pass
+   in flight reads, after that copy's last readers, and that copy becomes
+   current; a pass already queued keeps the epoch it started with.  A filter
+   id past the slots makes the commit a full upload. */
+int egm_routes_commit(egm_ctx* ctx, uint64_t* epoch);
+/* The last commit: masks patched, and whether it was a full upload. */
+int egm_routes_last_commit(egm_ctx* ctx, uint64_t* patched, int* rebuilt);
+/* <- cleanup_routes/1 (apps/emqx/src/emqx_router_helper.erl:137-146,
+   175-179) for the atom-dest pattern: every route to `node` is removed in one
+   streaming device pass (staged changes are committed with it), and the
+   filter ids left without any route are returned, sorted ascending
+   (*emptied_fids is NULL when *n == 0; free with egm_result_free).  The
+   caller deletes those filters from the match table itself.  The
+   {Group, Node} pattern of cleanup_routes is not covered: the subscriber and
+   share tables carry no node.  Dropping a node nobody routes to returns an
+   empty list. */
+int egm_routes_drop_node(egm_ctx* ctx, uint32_t node, uint32_t** emptied_fids, uint64_t* n);
+/* <- route/2's forward arm over a device match CSR (emqx_broker.erl:242-247,
+   262-280), with aggre/1's once-per-{To, Node} rule (:249-260): the masks are
+   sets and EGM_MODE_ROUTES rows are sets, so each (row, filter, node) appears
+   exactly once.  Node n's forwards are (d_fwd_topic[j], d_fwd_fid[j]) for j in
+   [d_node_row[n], d_node_row[n + 1]), ordered by (match row index, position
+   inside the row); d_node_row holds EGM_ROUTE_MAX_NODES + 1 entries and the
+   local node's row is empty.  "Topic" is the row index of the CSR given (with
+   walk-order rows the caller maps it through d_topic).  d_entry_fwd[i]
+   (nullable, match_ids entries) = remote nodes of match entry i, bit 31 set
+   if its filter has a local route; d_topic_fwd[k] (nullable, n_topics) =
+   forwards of row k: the messages.forward count.  match_ids_len as in
+   egm_fanout_device (EGM_E_OVERFLOW before any kernel reads the ids).  When
+   the total exceeds fwd_cap, d_node_row and the two count arrays are still
+   written, nothing is written to the lists and egm_last_forward reports the
+   total.  EGM_E_STATE before egm_routes_build.  Asynchronous on hip_stream
+   (NULL = the HIP default stream). */
+int egm_forward_device(egm_ctx* ctx, const uint64_t* d_match_row, const uint32_t* d_match_ids,
+                       uint64_t match_ids_len, uint32_t n_topics, void* hip_stream, uint64_t* d_node_row,
+                       uint32_t* d_fwd_topic, uint32_t* d_fwd_fid, uint64_t fwd_cap, uint32_t* d_entry_fwd,
+                       uint32_t* d_topic_fwd);
+/* Host form: the plain result form only (as egm_fanout_batch), retried with
+   the reported size when its first guess is too small; free with
+   egm_result_free. */
+typedef struct egm_forward {
+  uint32_t n_topics;
+  uint32_t n_nodes;        /* EGM_ROUTE_MAX_NODES */
+  uint64_t n_entries;      /* matched ids of the batch */
+  uint64_t n_forwards;
+  uint64_t* node_row;      /* [n_nodes+1] */
+  uint32_t* topic;         /* [n_forwards] */
+  uint32_t* fid;           /* [n_forwards] */
+  uint32_t* entry_fwd;     /* [n_entries] */
+  uint32_t* topic_fwd;     /* [n_topics] */
+} egm_forward;
+int egm_forward_batch(egm_ctx* ctx, const egm_result* matched, egm_forward** out);
+/* Synchronises the last forward pass and reports its total and whether
+   fwd_cap was too small (overflow != 0: the lists were not written). */
+int egm_last_forward(egm_ctx* ctx, uint64_t* n_forwards, uint32_t* overflow);
+/* Accumulated time (ms) and launches of the forward pass, under egm_set_timing. */
+int egm_get_forward_timing(egm_ctx* ctx, double* ms, uint64_t* launches);
+
 /* ---- multi-GPU filter sharding ----
    Merge the match results of one topic batch against n_shards disjoint filter
    shards (each matched on its own GPU, gathered here over RCCL) into one CSR:

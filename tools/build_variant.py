@@ -21,7 +21,7 @@ bdir = f"/tmp/egm_var_{tag}"
 os.makedirs(bdir, exist_ok=True)
 objs = []
 for name in B.HIP_SOURCES:
-    objs.append(os.path.join(bdir, name.replace(".hip", ".o")))
+    objs.append(os.path.join(bdir, name + ".o"))
     B._run([B._hipcc(), f"--offload-arch={B.ARCH}", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result",
             "-Wno-unused-value", *flags, "-c", os.path.join(B.CSRC, name), "-o", objs[-1]], True)
 for name in B.HOST_SOURCES:
